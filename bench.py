@@ -11,8 +11,16 @@ forward, NLL loss, backward, gradient all-reduce (world > 1) and the SGD update.
 Data is synthetic (a learnable MNIST-shaped dataset resident in HBM), weights are
 random-init (torch.manual_seed + the reference's default init).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--kernels hip|torch]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--kernels hip|torch] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the
+result line.  ``--full`` adds the measurements that take runs of their own -- today the PyTorchJob
+started through the native operator after the timed region (``create_to_first_step_s`` and ``job``
+in the line; ``--job-latency 0`` skips it even then).  ``--dump-outputs DIR`` writes what the last
+timed step left with its caller -- the updated parameters, the momentum buffers, the step's loss
+and correct count -- as float32 ``DIR/<name>.npy`` (rank 0's; the data and the initial weights are
+seeded, so the same arguments give the same inputs in every run).
 
 ``python bench.py --gpus N`` with N > 1 and no launcher (no ``WORLD_SIZE`` in the env) starts
 the N ranks itself: before importing torch or touching HIP it runs ``torch.distributed.run
@@ -87,9 +95,15 @@ def parse_args(argv=None):
                         "all-reduces every step, racing the RCCL step forms (their single-rank floor; "
                         "not the headline configuration)")
     p.add_argument("--json-out", default=None)
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's results (params, momentum, "
+                        "stats = loss and correct count) as float32 DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the PyTorchJob latency "
+                        "measurement after the timed region (see --job-latency)")
     p.add_argument("--job-latency", type=int, default=1,
-                   help="after the timed region, run one PyTorchJob with one pod per GPU through "
-                        "the native operator + local cluster and report create->first-step (1/0)")
+                   help="with --full: after the timed region, run one PyTorchJob with one pod per GPU "
+                        "through the native operator + local cluster and report create->first-step (1/0)")
     p.add_argument("--job-timeout", type=float, default=150.0)
     p.add_argument("--job-gpus", default="",
                    help="node GPU ids of the job's pods, comma-separated (default 0..N-1); repeated ids "
@@ -100,7 +114,11 @@ def parse_args(argv=None):
                    help="keep the GPU busy (FMA spin, no training state touched) this long before "
                         "the warm-up steps so the timed steps run at steady-state clocks "
                         "(profiles/r2_cold_start.json); 0 = off")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps_per_graph > 0 and args.steps % args.steps_per_graph:
+        p.error(f"--steps {args.steps} is not a multiple of --steps-per-graph {args.steps_per_graph}: "
+                "exactly --steps steps are timed")
+    return args
 
 
 SELF_LAUNCH_ENV = "PTO_BENCH_LAUNCHER"
@@ -284,6 +302,15 @@ def prewarm(ms: int, dev) -> None:
     torch.cuda.synchronize(dev)
 
 
+def dump_outputs(dirpath: str, arrays: dict) -> None:
+    """``--dump-outputs``: each tensor as float32 ``dirpath/<name>.npy``."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse_args(argv)
@@ -364,7 +391,9 @@ def main(argv=None):
 
         def run(n):
             runner.run(n)
-        steps = args.steps - args.steps % runner.steps_per_graph
+        steps = args.steps
+        if steps % runner.steps_per_graph:  # parse_args refuses the only way to get here
+            raise ValueError(f"--steps {steps} is not a multiple of the timed graph's {runner.steps_per_graph}")
         xgmi_error = (lambda: xg.xar.error()) if xg is not None else (lambda: 0)
         mode_desc = (f"{args.mode}(launch={runner.launch},spg={runner.steps_per_graph},"
                      f"allreduce={ar_path},conv_chunk={args.conv_chunk},stage={args.stage})")
@@ -387,6 +416,7 @@ def main(argv=None):
                 state["i"] = i + 1
                 opt.zero_grad(set_to_none=True)
                 loss = F.nll_loss(model(xf[idx]), lab[idx])
+                state["loss"] = loss
                 loss.backward()
                 opt.step()
         prewarm(args.prewarm_ms, dev)
@@ -434,9 +464,20 @@ def main(argv=None):
         in_sync = bool(float(diff.item()) == 0.0) and ar_err == 0
     nranks = rccl_nranks()
 
+    if args.dump_outputs and rank == 0:
+        if args.kernels == "hip":
+            outs = {"params": tr.flat_params, "momentum": tr.flat_momentum, "stats": tr.stats[:2]}
+        else:
+            ps = list(model.parameters())
+            outs = {"params": torch.cat([q.detach().reshape(-1) for q in ps]),
+                    "momentum": torch.cat([opt.state[q]["momentum_buffer"].reshape(-1) for q in ps]),
+                    "stats": state["loss"].detach().reshape(1)}
+        dump_outputs(args.dump_outputs, outs)
+
     # a forced-collectives bench forces them in the job's pods too (their race lands in job.allreduce_trial)
     lat = job_latency(world, rank, args.job_timeout, *job_plan,
-                      extra_args=("--force-collectives", "1") if force else ()) if args.job_latency else {}
+                      extra_args=("--force-collectives", "1") if force else ()) \
+        if args.full and args.job_latency else {}
 
     samples = steps * B * world
     value = samples / dt

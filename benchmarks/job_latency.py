@@ -110,7 +110,7 @@ def measure(replicas: int, gpus=None, backend: str = "rccl", timeout: float = 18
     """One job of ``replicas`` pods through the real operator (1 GPU per pod when ``gpus``
     lists node GPU ids) on a kubelet that isolates pods like a real one where the host
     allows it (docs/xgmi_pods.md); the dict of ``run_one`` plus how the pods were placed.
-    Used by bench.py after its timed region."""
+    Used by ``bench.py --full`` after its timed region."""
     args = ["--backend", backend, *extra_args]
     gpu = bool(gpus)
     if not gpu:

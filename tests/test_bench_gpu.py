@@ -3,7 +3,7 @@
 process-group backend (RCCL wants one GPU per rank) and both ranks sharing cuda:0.
 
 Checks the JSON line's DDP invariants (n_gpus, replicas_in_sync, grad_allreduce_error)
-and the PyTorchJob it runs after the timed region: two pods through the real operator and
+and the PyTorchJob it runs after the timed region with ``--full``: two pods through the real operator and
 kubelet emulator (``--job-gpus 0,0`` lets them share the GPU), Succeeded, with the pods'
 steady-state step-time percentiles in the line.
 """
@@ -51,6 +51,34 @@ def test_bench_self_launch(tmp_path):
         (Path(rec) / "bench_self_launch_w2.json").write_text(json.dumps(line))
 
 
+@pytest.mark.timeout(120)
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """The plain command ``bench.py --gpus 1 --steps K --warmup W``: exactly K timed steps, no
+    PyTorchJob (that is ``--full``), and ``--dump-outputs`` writes the last step's results."""
+    import numpy as np
+    from pytorch_operator_amd.models.mnist import flat_layout
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["PYTHONPATH"] = str(ROOT)
+    dump = tmp_path / "outs"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=100, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith('{"metric"')][0])
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["ms_per_step"] > 0, line
+    assert line["metric"] == "mnist_ddp_train_samples_per_sec" and line["unit"] == "samples/s", line
+    assert line["higher_is_better"] is True and line["dtype"] == "fp32", line
+    assert abs(line["value"] - 64 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"], line
+    assert "job" not in line and "create_to_first_step_s" not in line, line
+    arrs = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(arrs) == {"params", "momentum", "stats"}, sorted(arrs)
+    L = flat_layout().total
+    assert arrs["params"].shape == (L,) and arrs["momentum"].shape == (L,) and arrs["stats"].shape == (2,)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    loss, correct = arrs["stats"]
+    assert 0 < loss < 10 and 0 <= correct <= 64 and np.abs(arrs["momentum"]).max() > 0, arrs["stats"]
+
+
 @pytest.mark.timeout(200)
 def test_bench_rccl_nranks_world1(tmp_path):
     """Forced single-rank RCCL group: the line carries the communicator's own rank count."""
@@ -88,7 +116,7 @@ def test_bench_two_ranks_one_gpu(tmp_path, allreduce):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), str(ROOT / "bench.py"),
            "--gpus", "2", "--backend", "gloo", "--allreduce", allreduce, "--steps", "20", "--warmup", "5",
-           "--job-gpus", "0,0", "--job-timeout", "200", "--json-out", str(out)]
+           "--full", "--job-gpus", "0,0", "--job-timeout", "200", "--json-out", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=380, cwd=ROOT, env=env)
     assert r.returncode == 0 and out.exists(), r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads(out.read_text())

@@ -50,6 +50,31 @@ def test_check_line():
     assert "RCCL" in bench.check_line(dict(ok, rccl_nranks=1), 4)
 
 
+def test_plain_run_options():
+    """``--full`` is off by default (the job-latency run needs it), ``--dump-outputs`` names a
+    directory, and a ``--steps`` that the timed graph cannot run exactly is refused, not rounded."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20
+    a = bench.parse_args(["--full", "--dump-outputs", "/x/outs"])
+    assert a.full is True and a.job_latency == 1 and a.dump_outputs == "/x/outs"
+    assert bench.parse_args(["--steps", "20", "--steps-per-graph", "5"]).steps_per_graph == 5
+    with pytest.raises(SystemExit) as e:
+        bench.parse_args(["--steps", "20", "--steps-per-graph", "7"])
+    assert e.value.code == 2
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    import numpy as np
+    import torch
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), {"params": torch.arange(6, dtype=torch.float64).view(2, 3)[:, 1:],
+                                "stats": torch.tensor([1.5, 2.0])})
+    assert sorted(p.name for p in d.iterdir()) == ["params.npy", "stats.npy"]
+    p = np.load(d / "params.npy")
+    assert p.dtype == np.float32 and p.tolist() == [[1.0, 2.0], [4.0, 5.0]]
+    assert np.load(d / "stats.npy").tolist() == [1.5, 2.0]
+
+
 @pytest.mark.timeout(120)
 def test_world_size_mismatch_exits_2():
     """Launched with WORLD_SIZE=2 but --gpus 1 (or the reverse): exit 2, no line, no torch import."""

@@ -61,7 +61,7 @@ def test_bench_forced_collectives_world1_through_operator(tmp_path):
     and in the operator-deployed pod's events (VERDICT r4 #7)."""
     out = tmp_path / "bench.json"
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--backend", "nccl", "--force-collectives", "1",
-           "--steps", "20", "--warmup", "5", "--job-timeout", "200", "--json-out", str(out)]
+           "--steps", "20", "--warmup", "5", "--full", "--job-timeout", "200", "--json-out", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=380, cwd=ROOT, env=_env())
     assert r.returncode == 0 and out.exists(), r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads(out.read_text())

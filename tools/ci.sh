@@ -20,7 +20,7 @@ case "$mode" in
   gpu)
     timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()"
-    timeout -k 10 300 python bench.py --steps 2000 --warmup 50
+    timeout -k 10 300 python bench.py --steps 2000 --warmup 50 --full
     ;;
   *)
     echo "usage: tools/ci.sh cpu|gpu" >&2
