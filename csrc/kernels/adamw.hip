@@ -38,10 +38,19 @@ __device__ __forceinline__ float adam1(float& p, float& m, float& v, float g, co
   return p;
 }
 
-template <bool GBF16, bool OUTBF16>
+// CLIP: global-norm gradient clipping.  `sumsq` is the device scalar sum(g^2) over ALL gradients
+// of the step (gradclip.hip); every thread loads it once and folds torch.nn.utils.clip_grad_norm_'s
+// coefficient min(1, max_norm / (norm + 1e-6)) into the gradient scale.  A NaN norm propagates
+// (the comparison is false), as torch's clamp does.
+template <bool GBF16, bool OUTBF16, bool CLIP>
 __global__ __launch_bounds__(kT) void adamw_kernel(float* __restrict__ master, float* __restrict__ mom,
                                                    float* __restrict__ var, const void* __restrict__ grad,
-                                                   uint16_t* __restrict__ out, long n, AdamArgs a) {
+                                                   uint16_t* __restrict__ out, long n, AdamArgs a,
+                                                   const float* __restrict__ sumsq, float max_norm) {
+  if (CLIP) {
+    const float c = max_norm / (sqrtf(sumsq[0]) + 1e-6f);
+    a.gscale *= c > 1.f ? 1.f : c;
+  }
   const long n4 = n / 4;
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i <= n4; i += (long)gridDim.x * kT) {
     if (i < n4) {
@@ -84,14 +93,12 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-// grad_bf16: gradient dtype (1 = bf16, 0 = fp32).  out: bf16 weight to refresh (nullptr for
-// fp32 parameters, whose master IS the parameter).  step >= 1.  grad_scale multiplies the
-// gradient first (ZeRO's gradient-view buckets hold the unscaled sum over ranks).
-int pto_adamw_step_scaled(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16,
-                          float lr, float b1, float b2, float eps, float wd, int step, float grad_scale,
-                          void* stream) {
+template <bool CLIP>
+int launch_adamw(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16, float lr,
+                 float b1, float b2, float eps, float wd, int step, float grad_scale, const float* sumsq,
+                 float max_norm, void* stream) {
   if (n <= 0 || step < 1) return -1;
   if (!aligned16(master) || !aligned16(m) || !aligned16(v) || !aligned16(grad) || (out && !aligned16(out)))
     return -2;
@@ -104,20 +111,45 @@ int pto_adamw_step_scaled(float* master, float* m, float* v, const void* grad, v
   if (blocks > 8192) blocks = 8192;  // 32 waves per CU resident at most; grid-stride beyond
   const dim3 grid((unsigned)blocks), block(kT);
   hipStream_t s = (hipStream_t)stream;
-  if (grad_bf16 && out) hipLaunchKernelGGL((adamw_kernel<true, true>), grid, block, 0, s, master, m, v, grad,
-                                           (uint16_t*)out, n, a);
-  else if (grad_bf16) hipLaunchKernelGGL((adamw_kernel<true, false>), grid, block, 0, s, master, m, v, grad,
-                                         (uint16_t*)nullptr, n, a);
-  else if (out) hipLaunchKernelGGL((adamw_kernel<false, true>), grid, block, 0, s, master, m, v, grad,
-                                   (uint16_t*)out, n, a);
-  else hipLaunchKernelGGL((adamw_kernel<false, false>), grid, block, 0, s, master, m, v, grad,
-                          (uint16_t*)nullptr, n, a);
+  if (grad_bf16 && out) hipLaunchKernelGGL((adamw_kernel<true, true, CLIP>), grid, block, 0, s, master, m, v, grad,
+                                           (uint16_t*)out, n, a, sumsq, max_norm);
+  else if (grad_bf16) hipLaunchKernelGGL((adamw_kernel<true, false, CLIP>), grid, block, 0, s, master, m, v, grad,
+                                         (uint16_t*)nullptr, n, a, sumsq, max_norm);
+  else if (out) hipLaunchKernelGGL((adamw_kernel<false, true, CLIP>), grid, block, 0, s, master, m, v, grad,
+                                   (uint16_t*)out, n, a, sumsq, max_norm);
+  else hipLaunchKernelGGL((adamw_kernel<false, false, CLIP>), grid, block, 0, s, master, m, v, grad,
+                          (uint16_t*)nullptr, n, a, sumsq, max_norm);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+// grad_bf16: gradient dtype (1 = bf16, 0 = fp32).  out: bf16 weight to refresh (nullptr for
+// fp32 parameters, whose master IS the parameter).  step >= 1.  grad_scale multiplies the
+// gradient first (ZeRO's gradient-view buckets hold the unscaled sum over ranks).
+int pto_adamw_step_scaled(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16,
+                          float lr, float b1, float b2, float eps, float wd, int step, float grad_scale,
+                          void* stream) {
+  return launch_adamw<false>(master, m, v, grad, out, n, grad_bf16, lr, b1, b2, eps, wd, step, grad_scale, nullptr,
+                             0.f, stream);
 }
 
 int pto_adamw_step(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16,
                    float lr, float b1, float b2, float eps, float wd, int step, void* stream) {
   return pto_adamw_step_scaled(master, m, v, grad, out, n, grad_bf16, lr, b1, b2, eps, wd, step, 1.f, stream);
+}
+
+// pto_adamw_step_scaled with the gradient also multiplied by min(1, max_norm / (sqrt(*sumsq) + 1e-6)):
+// sumsq is the DEVICE scalar pto_grad_sumsq_finish wrote (the host never reads it).
+int pto_adamw_step_clipped(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16,
+                           float lr, float b1, float b2, float eps, float wd, int step, float grad_scale,
+                           const float* sumsq, float max_norm, void* stream) {
+  if (!sumsq || ((uintptr_t)sumsq & 3u)) return -2;
+  if (!(max_norm > 0.f)) return -1;
+  return launch_adamw<true>(master, m, v, grad, out, n, grad_bf16, lr, b1, b2, eps, wd, step, grad_scale, sumsq,
+                            max_norm, stream);
 }
 
 }  // extern "C"

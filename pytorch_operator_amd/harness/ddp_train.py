@@ -96,6 +96,10 @@ def parse_args(argv=None):
                    help="checkpoint directory (utils/train_ckpt.py): resume from it if it holds one, save "
                         "there at the end (and every --ckpt-every steps); shared by all ranks")
     p.add_argument("--ckpt-every", type=int, default=0)
+    p.add_argument("--max-grad-norm", type=float, default=0.0,
+                   help="clip gradients by their global L2 norm (torch.nn.utils.clip_grad_norm_'s rule) "
+                        "before the optimizer step; 0 = off.  Master-weight / ZeRO Llama: computed on the "
+                        "device inside the optimizer (csrc/kernels/gradclip.hip)")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
@@ -141,6 +145,7 @@ def build(args, device, world: int = 1):
     RMSNorm.fuse_residual = args.residual_norm == "fused"
     with torch.device(device):
         model = Llama(CONFIGS[args.model], checkpoint_layers=args.grad_checkpoint)
+    clip = {"max_grad_norm": args.max_grad_norm} if args.max_grad_norm > 0 else {}
     if use_zero(args, device, world):
         from ..ops.optim import to_bf16_matmul_weights
         from ..parallel.zero import ZeroAdamW
@@ -151,14 +156,14 @@ def build(args, device, world: int = 1):
         opt = ZeroAdamW(model, lr=args.lr or 3e-4, betas=(0.9, 0.95), weight_decay=0.1,
                         bucket_mb=args.zero_bucket_mb,
                         reduce_dtype=torch.bfloat16 if args.allreduce_dtype == "bf16" else torch.float32,
-                        grad_view=bool(args.zero_grad_view))
+                        grad_view=bool(args.zero_grad_view), **clip)
         return model, opt
     if use_master_weights(args, device):
         from ..ops.optim import MasterAdamW, install_overlap, to_bf16_matmul_weights
         to_bf16_matmul_weights(model)
         overlap = args.opt_overlap == "on" and device.type == "cuda"
         opt = MasterAdamW(model.parameters(), lr=args.lr or 3e-4, betas=(0.9, 0.95), weight_decay=0.1,
-                          overlap=overlap)
+                          overlap=overlap, **clip)
         if overlap:
             install_overlap(model)
         return model, opt
@@ -326,8 +331,17 @@ def main(argv=None) -> int:
     if gstep and rank == 0:
         print(json.dumps({"event": "resumed", "step": gstep, "dir": args.ckpt_dir}), flush=True)
 
+    # gradient clipping: inside MasterAdamW / ZeroAdamW (they own the gradients), or torch's
+    # clip_grad_norm_ in front of a plain torch optimizer
+    clip = args.max_grad_norm if args.max_grad_norm > 0 else None
+    torch_clip = clip is not None and not hasattr(opt, "last_grad_norm")
+    torch_norm = None
+
+    def grad_norm() -> float:
+        return float(torch_norm if torch_clip else opt.last_grad_norm())
+
     def step():
-        nonlocal gstep
+        nonlocal gstep, torch_norm
         gstep += 1
         if args.ckpt_dir and args.ckpt_every and gstep % args.ckpt_every == 0:
             pending_ckpt.append(gstep)
@@ -338,6 +352,8 @@ def main(argv=None) -> int:
             else:
                 loss = F.cross_entropy(model(x).float(), y)
         loss.backward()
+        if torch_clip:
+            torch_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
         opt.step()
         if pending_ckpt:
             train_ckpt.save(args.ckpt_dir, pending_ckpt.pop(), bare, opt, rank, world)
@@ -353,9 +369,11 @@ def main(argv=None) -> int:
     loss = step()
     sync()
     if rank == 0:
-        print(json.dumps({"event": "first_step", "rank": rank, "unix_ns": time.time_ns(),
-                          "first_step_s": round((time.time_ns() - t_start) / 1e9, 3),
-                          "loss": float(loss)}), flush=True)
+        first = {"event": "first_step", "rank": rank, "unix_ns": time.time_ns(),
+                 "first_step_s": round((time.time_ns() - t_start) / 1e9, 3), "loss": float(loss)}
+        if clip is not None:
+            first["grad_norm"] = grad_norm()
+        print(json.dumps(first), flush=True)
     for _ in range(max(0, args.warmup - 1)):
         step()
     sync()
@@ -391,6 +409,8 @@ def main(argv=None) -> int:
         res.update(optimizer_state_gb_per_rank=round(opt.state_bytes() / 2 ** 30, 2), zero_buckets=len(opt.buckets),
                    zero_grad_sinks=opt.sinks, zero_grad_dtypes=sorted({str(b.gdt).replace("torch.", "") for b in opt.buckets}))
     res.update(gemm_tuning=tuning.get("mode"))
+    if clip is not None:
+        res.update(max_grad_norm=clip, grad_norm=grad_norm())
     if is_llama:
         res.update(attn=args.attn, residual_norm=args.residual_norm, linear_bwd=args.linear_bwd,
                    opt_overlap=args.opt_overlap if res["master_weights"] and not zero else None)

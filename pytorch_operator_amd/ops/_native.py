@@ -189,6 +189,10 @@ _SIGNATURES = {
     # adamw.hip
     "pto_adamw_step": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _VP],
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
+    "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
+    # gradclip.hip
+    "pto_grad_sumsq": [_VP, _L, _I, _F, _VP, _L, _VP],
+    "pto_grad_sumsq_finish": [_VP, _L, _VP, _VP],
     # batchnorm.hip
     "pto_bn_plan": [_L, _I, ctypes.POINTER(_I)],
     "pto_bn_fwd_train": [_VP] * 12 + [_L, _I, _I, _I, _F, _F, _I, _I, _VP, _VP],
@@ -213,7 +217,7 @@ _SIGNATURES = {
     "pto_device_prewarm": [_I, _VP, _VP],
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
-             "pto_graph_nodes": [_VP]}
+             "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I]}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

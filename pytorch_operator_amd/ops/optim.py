@@ -42,12 +42,31 @@ class MasterAdamW(torch.optim.Optimizer):
     (model)`` makes every module wait (on the compute stream) for its own parameters' events
     just before its forward.  The next step's forward then starts while the updates of the
     later layers are still streaming -- the memory-bound optimizer (~11 % of a Llama-3 8B
-    step) runs under the compute-bound forward GEMMs instead of after them."""
+    step) runs under the compute-bound forward GEMMs instead of after them.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, overlap=False):
+    ``max_grad_norm`` (default ``None``: off, nothing below runs): clip the gradients by their
+    global L2 norm, ``torch.nn.utils.clip_grad_norm_``'s rule (``error_if_nonfinite=False``), over
+    exactly the tensors the step consumes.  On the GPU that is one streaming sum-of-squares pass
+    per gradient, one finish launch, and the AdamW launches reading the result on the device
+    (``csrc/kernels/gradclip.hip``); the host never sees the norm unless it asks
+    (``last_grad_norm()``)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, overlap=False,
+                 max_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.overlap = overlap
         self._side = None
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("max_grad_norm: a positive number, or None for no clipping")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._norm = None      # DeviceGradNorm (GPU), created by the first clipped step
+        self._norm_out = None  # [sum of squares, norm] of the last clipped step
+
+    def last_grad_norm(self):
+        """Global gradient norm of the last ``step()`` before clipping, as a 0-dim tensor on the
+        parameters' device (``None`` without ``max_grad_norm`` or before the first step).  Does not
+        synchronise: with ``overlap=True`` the value is written on the side stream."""
+        return None if self._norm_out is None else self._norm_out[1]
 
     def _state(self, p):
         st = self.state[p]
@@ -90,6 +109,8 @@ class MasterAdamW(torch.optim.Optimizer):
         return loss
 
     def _step_all(self, side):
+        if self.max_grad_norm is not None:
+            return self._step_all_clipped(side)
         for group in self.param_groups:
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             for p in group["params"]:
@@ -116,6 +137,56 @@ class MasterAdamW(torch.optim.Optimizer):
                 else:
                     self._step_reference(p, g, master, st, lr, b1, b2, eps, wd)
 
+    def _step_all_clipped(self, side):
+        """Two passes over the gradients this step consumes: their global norm, then AdamW with
+        the clip factor (on the GPU both on the current stream -- the side stream under overlap)."""
+        work = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError(f"MasterAdamW: fp32/bf16 parameters only, got {p.dtype}")
+                g32 = getattr(p, "_pto_grad32", None)
+                if g32 is not None:
+                    del p._pto_grad32
+                g = g32 if g32 is not None else p.grad
+                if p.is_cuda:
+                    if side is not None:
+                        g.record_stream(side)
+                    g = self._hip_grad(p, g)  # fixed up once, read by both passes
+                work.append((group, p, g))
+        if not work:
+            return
+        if len({p.is_cuda for _, p, _ in work}) > 1:
+            raise ValueError("MasterAdamW(max_grad_norm): parameters on the GPU and on the CPU in one optimizer")
+        cuda = work[0][1].is_cuda
+        if cuda:
+            from .gradclip import DeviceGradNorm
+            if self._norm is None:
+                self._norm = DeviceGradNorm()
+            self._norm_out = self._norm.run([(g, 1.0) for _, _, g in work if g.numel()])
+            coef = None
+        else:
+            from .gradclip import clip_coef
+            sumsq = torch.zeros((), dtype=torch.float32)
+            for _, _, g in work:
+                sumsq += g.float().pow(2).sum()
+            self._norm_out = torch.stack([sumsq, sumsq.sqrt()])
+            coef = clip_coef(self._norm_out[1], self.max_grad_norm)
+        for group, p, g in work:
+            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+            st = self._state(p)
+            st["step"] += 1
+            master = st["master"] if st["master"] is not None else p
+            if cuda:
+                self._launch_hip(p, g, master, st, lr, b1, b2, eps, wd, clip=(self._norm_out, self.max_grad_norm))
+                if side is not None:
+                    ev = torch.cuda.Event()
+                    ev.record(side)
+                    p._pto_ready = ev
+            else:
+                self._step_reference(p, g.float() * coef, master, st, lr, b1, b2, eps, wd)
 
     @staticmethod
     def _step_reference(p, g, master, st, lr, b1, b2, eps, wd):
@@ -130,17 +201,34 @@ class MasterAdamW(torch.optim.Optimizer):
             p.copy_(master)
 
     @staticmethod
-    def _step_hip(p, g, master, st, lr, b1, b2, eps, wd):
+    def _hip_grad(p, g):
+        """The gradient as the kernels read it: contiguous and 16-byte aligned."""
         if not g.is_contiguous() or g.data_ptr() % 16:
             g = g.contiguous().clone()
         if g.dtype not in (torch.float32, torch.bfloat16) or not p.is_contiguous():
             raise TypeError("MasterAdamW: contiguous fp32/bf16 parameters and gradients only")
+        return g
+
+    @classmethod
+    def _step_hip(cls, p, g, master, st, lr, b1, b2, eps, wd):
+        cls._launch_hip(p, cls._hip_grad(p, g), master, st, lr, b1, b2, eps, wd)
+
+    @staticmethod
+    def _launch_hip(p, g, master, st, lr, b1, b2, eps, wd, clip=None):
         out = p.data_ptr() if master is not p else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-        _native.check(_native.load().pto_adamw_step(
-            master.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), g.data_ptr(), out,
-            p.numel(), 1 if g.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd, st["step"], stream),
-            "adamw_step")
+        lib = _native.load()
+        if clip is None:
+            _native.check(lib.pto_adamw_step(
+                master.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), g.data_ptr(), out,
+                p.numel(), 1 if g.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd, st["step"], stream),
+                "adamw_step")
+        else:
+            sumsq, max_norm = clip  # the device scalar of gradclip.hip's finish kernel
+            _native.check(lib.pto_adamw_step_clipped(
+                master.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), g.data_ptr(), out,
+                p.numel(), 1 if g.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd, st["step"], 1.0,
+                sumsq.data_ptr(), max_norm, stream), "adamw_step_clipped")
 
 
 def install_overlap(model: nn.Module) -> int:

@@ -136,10 +136,28 @@ class _Bucket:
 class ZeroAdamW:
     """Replaces ``DDP(model) + MasterAdamW``: construct on the (unwrapped) model after
     ``to_bf16_matmul_weights``; call ``zero_grad`` / forward / backward / ``step`` as usual.
-    Weights are broadcast from rank 0 at construction (DDP constructor semantics)."""
+    Weights are broadcast from rank 0 at construction (DDP constructor semantics).
+
+    ``max_grad_norm`` (default ``None``: off, ``step()`` is the single per-bucket loop): clip by the
+    global L2 norm of the averaged gradient, ``torch.nn.utils.clip_grad_norm_``'s rule.  ``step()``
+    then makes two passes.  Pass 1 waits for every bucket's reduce-scatter and launches the
+    sum-of-squares kernel (``csrc/kernels/gradclip.hip``) over this rank's shard (1/W folded in
+    for unscaled buckets; the zero padding adds nothing); one finish launch leaves the rank's
+    sum in a device float, and at world > 1 one all-reduce (SUM) of that single fp32 gives every
+    rank the same bytes, hence the same clip factor.  Pass 2 is the per-bucket AdamW + all-gather
+    loop, its kernel reading the sum on the device.  The global norm needs every bucket reduced
+    before the first update, so the first weight all-gather starts one gradient read later than
+    without clipping; that is inherent to clipping by global norm."""
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 group=None, bucket_mb: float = 256.0, reduce_dtype=torch.float32, grad_view: bool = True):
+                 group=None, bucket_mb: float = 256.0, reduce_dtype=torch.float32, grad_view: bool = True,
+                 max_grad_norm=None):
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("max_grad_norm: a positive number, or None for no clipping")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._norm = None      # ops.gradclip.DeviceGradNorm (GPU), created by the first clipped step
+        self._norm_out = None  # [sum of squares, norm] of the last clipped step
+        self._coef = None      # CPU path: the clip factor of the current step
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -282,6 +300,8 @@ class ZeroAdamW:
                         self._deposit(b.grad32[off:off + p.numel()], p.grad.reshape(-1), b.unscaled)
                         p.grad = None
                 self._reduce_scatter(b)
+        if self.max_grad_norm is not None:
+            self._grad_norm_pass()
         # forward order (the last bucket holds the first layers): their all-gathers go first
         for b in reversed(self.buckets):
             if b.rs_work is not None:
@@ -316,6 +336,40 @@ class ZeroAdamW:
             b.arrived.clear()
         return loss
 
+    def _grad_norm_pass(self) -> None:
+        """Pass 1 of a clipped step: global norm of the averaged gradient, left on the device."""
+        items = []
+        for b in reversed(self.buckets):
+            if b.rs_work is not None:
+                b.rs_work.wait()
+                b.rs_work = None
+            if self.world > 1:
+                b.release_grad()
+            items.append((b.gshard, 1.0 / self.world if b.unscaled else 1.0))
+        if items[0][0].is_cuda:
+            from ..ops.gradclip import DeviceGradNorm
+            if self._norm is None:
+                self._norm = DeviceGradNorm()
+            out = self._norm_out = self._norm.run(items)
+            if self.world > 1:
+                dist.all_reduce(out[:1], op=dist.ReduceOp.SUM, group=self.group)
+                torch.sqrt(out[:1], out=out[1:])
+        else:
+            from ..ops.gradclip import clip_coef
+            sumsq = torch.zeros(1, dtype=torch.float32)
+            for g, scale in items:
+                sumsq += (g.float() * scale).pow(2).sum()
+            if self.world > 1:
+                dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.group)
+            self._norm_out = torch.cat([sumsq, sumsq.sqrt()])
+            self._coef = clip_coef(self._norm_out[1], self.max_grad_norm)
+
+    def last_grad_norm(self):
+        """Global norm of the averaged gradient at the last ``step()``, before clipping, as a 0-dim
+        tensor on the parameters' device (``None`` without ``max_grad_norm`` or before the first
+        step).  Does not synchronise."""
+        return None if self._norm_out is None else self._norm_out[1]
+
     @staticmethod
     def _save_ranges(b: _Bucket, ranges) -> list:
         """Copies of the optimizer state + weights of the bucket ranges AdamW must not touch
@@ -344,6 +398,13 @@ class ZeroAdamW:
             from ..ops import _native
             stream = ctypes.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
             out = w.data_ptr() if b.master is not None else None
+            if self.max_grad_norm is not None:
+                _native.check(_native.load().pto_adamw_step_clipped(
+                    master.data_ptr(), b.exp_avg.data_ptr(), b.exp_avg_sq.data_ptr(), b.gshard.data_ptr(), out,
+                    b.shard, 1 if b.gshard.dtype == torch.bfloat16 else 0, self.lr, b1, b2, self.eps,
+                    self.weight_decay, t, 1.0 / self.world if b.unscaled else 1.0, self._norm_out.data_ptr(),
+                    self.max_grad_norm, stream), "adamw_step_clipped")
+                return
             _native.check(_native.load().pto_adamw_step_scaled(
                 master.data_ptr(), b.exp_avg.data_ptr(), b.exp_avg_sq.data_ptr(), b.gshard.data_ptr(), out,
                 b.shard, 1 if b.gshard.dtype == torch.bfloat16 else 0, self.lr, b1, b2, self.eps,
@@ -351,7 +412,8 @@ class ZeroAdamW:
         else:
             from ..ops.optim import MasterAdamW
             st = {"step": t, "exp_avg": b.exp_avg, "exp_avg_sq": b.exp_avg_sq}
-            MasterAdamW._step_reference(w, b.gshard, master, st, self.lr, b1, b2, self.eps, self.weight_decay)
+            g = b.gshard if self.max_grad_norm is None else b.gshard.float() * self._coef
+            MasterAdamW._step_reference(w, g, master, st, self.lr, b1, b2, self.eps, self.weight_decay)
 
     def _wait_weights(self, buckets) -> None:
         for b in buckets:
