@@ -100,6 +100,13 @@ def parse_args(argv=None):
                    help="clip gradients by their global L2 norm (torch.nn.utils.clip_grad_norm_'s rule) "
                         "before the optimizer step; 0 = off.  Master-weight / ZeRO Llama: computed on the "
                         "device inside the optimizer (csrc/kernels/gradclip.hip)")
+    p.add_argument("--doc-len-mean", type=int, default=0,
+                   help="Llama: pack documents into each sequence -- every position becomes the end-of-text "
+                        "token with probability 1/N, attention stays inside each document "
+                        "(csrc/kernels/attention_doc.hip) and the target after an end-of-text token is "
+                        "ignored; 0 = off (one document per sequence)")
+    p.add_argument("--eos-id", type=int, default=None,
+                   help="end-of-text token id for --doc-len-mean (default: the last vocabulary id)")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
@@ -317,7 +324,19 @@ def main(argv=None) -> int:
         from ..models.llama import CONFIGS
         V = CONFIGS[args.model].vocab_size
         data = torch.randint(0, V, (B, args.seq_len + 1), generator=g).to(dev)
+        doc_start = None
+        if args.doc_len_mean > 0:
+            from ..ops.attention import doc_starts_from_tokens, validate_doc_start
+            eos = V - 1 if args.eos_id is None else args.eos_id
+            # drawn after the tokens from the same generator: the default token stream is unchanged
+            cut = torch.rand(B, args.seq_len + 1, generator=g) < 1.0 / args.doc_len_mean
+            data = torch.where(cut.to(dev), torch.full_like(data, eos), data)
         x, y = data[:, :-1].contiguous(), data[:, 1:].contiguous()
+        if args.doc_len_mean > 0:
+            doc_start = doc_starts_from_tokens(x, eos)
+            validate_doc_start(doc_start)
+            y = y.masked_fill(x == eos, -100)  # that target would be the next document's first token
+            docs_per_seq = float((x[:, :-1] == eos).sum()) / B + 1.0
     else:
         H = args.image_size if args.model == "resnet50" else 32
         x = torch.randn(B, 3, H, H, generator=g).to(dev)
@@ -347,7 +366,9 @@ def main(argv=None) -> int:
             pending_ckpt.append(gstep)
         opt.zero_grad(set_to_none=True)
         with amp:
-            if is_llama:
+            if is_llama and doc_start is not None:
+                loss = model(x, y, doc_start=doc_start)
+            elif is_llama:
                 loss = model(x, y)
             else:
                 loss = F.cross_entropy(model(x).float(), y)
@@ -414,6 +435,8 @@ def main(argv=None) -> int:
     if is_llama:
         res.update(attn=args.attn, residual_norm=args.residual_norm, linear_bwd=args.linear_bwd,
                    opt_overlap=args.opt_overlap if res["master_weights"] and not zero else None)
+    if is_llama and doc_start is not None:
+        res.update(doc_len_mean=args.doc_len_mean, docs_per_seq=round(docs_per_seq, 2), attn_mask="document")
     if tuning.get("mode") == "tune" and rank == 0:
         import torch.cuda.tunable as tunable
         out = args.gemm_tuning_file or default_tuning_file()

@@ -132,12 +132,19 @@ class Attention(nn.Module):
         self.wqkv = TNLinear(cfg.dim, (self.nh + 2 * self.nkv) * self.hd)
         self.wo = TNLinear(self.nh * self.hd, cfg.dim)
 
-    def forward(self, x, cos, sin):
+    def forward(self, x, cos, sin, doc_start=None):
         B, S, _ = x.shape
         from ..ops import attention as A
         from ..ops.llm import rope_qkv
         q, k, v = rope_qkv(self.wqkv(x), cos, sin, self.nh, self.nkv)
-        if self.impl != "sdpa" and A.hip_supported(q, k, v):
+        if doc_start is not None:
+            # packed documents: attention stays inside each one; RoPE positions stay absolute
+            # (it is relative, so restarting them per document would change nothing)
+            if self.impl != "sdpa" and A.hip_supported(q, k, v):
+                o = A.flash_attention(q, k, v, causal=True, doc_start=doc_start)
+            else:
+                o = A.sdpa_bshd(q, k, v, causal=True, doc_start=doc_start)
+        elif self.impl != "sdpa" and A.hip_supported(q, k, v):
             o = A.flash_attention(q, k, v, causal=True)  # [B, S, H, D], no transposes
         else:
             o = A.sdpa_bshd(q, k, v, causal=True)
@@ -164,12 +171,12 @@ class Block(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x, delta, cos, sin):
+    def forward(self, x, delta, cos, sin, doc_start=None):
         """x: residual stream entering the block minus the previous block's FFN output
         ``delta`` (None for the first block): each residual add happens inside the next
         RMSNorm.  Returns (residual stream before the FFN add, FFN output)."""
         h, y = self.attention_norm.add_forward(x, delta)
-        h, y = self.ffn_norm.add_forward(h, self.attention(y, cos, sin))
+        h, y = self.ffn_norm.add_forward(h, self.attention(y, cos, sin, doc_start))
         return h, self.feed_forward(y)
 
 
@@ -194,15 +201,18 @@ class Llama(nn.Module):
             nn.init.normal_(blk.attention.wo.weight, std=std / math.sqrt(2 * self.cfg.n_layers))
             nn.init.normal_(blk.feed_forward.w2.weight, std=std / math.sqrt(2 * self.cfg.n_layers))
 
-    def forward(self, tokens: torch.Tensor, targets: Optional[torch.Tensor] = None):
+    def forward(self, tokens: torch.Tensor, targets: Optional[torch.Tensor] = None,
+                doc_start: Optional[torch.Tensor] = None):
+        """``doc_start`` [B, S] (``ops.attention.doc_starts_from_tokens``): packed documents, attention
+        does not cross their boundaries."""
         B, S = tokens.shape
         cos, sin = rope_tables(self.cfg.head_dim, S, self.cfg.rope_theta, tokens.device)
         h, d = self.tok_embeddings(tokens), None
         for blk in self.layers:
             if self.checkpoint_layers and self.training:
-                h, d = torch.utils.checkpoint.checkpoint(blk, h, d, cos, sin, use_reentrant=False)
+                h, d = torch.utils.checkpoint.checkpoint(blk, h, d, cos, sin, doc_start, use_reentrant=False)
             else:
-                h, d = blk(h, d, cos, sin)
+                h, d = blk(h, d, cos, sin, doc_start)
         logits = self.output(self.norm.add_forward(h, d)[1])
         if targets is None:
             return logits

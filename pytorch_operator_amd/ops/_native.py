@@ -51,7 +51,10 @@ def _sources():
 # own asm MFMAs, so the compiler's MFMAs (S, dP) write VGPRs that the VALU reads directly), and
 # no SLP vectorisation: packed f32 VALU beside MFMAs costs more issue time than two scalar ops
 # (MI355X_MICROARCH.md, constants table).
+# attention_doc.hip: attention.hip's flags, so that the code its document-masked passes share with
+# the plain 4-wave passes is generated the same way (they are bit-identical with one document).
 _FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "attention_doc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
 
 
@@ -203,6 +206,9 @@ _SIGNATURES = {
     "pto_attn_set_variant": [_I],
     "pto_attn_set_dkdv_variant": [_I],
     "pto_attn_set_dq_variant": [_I],
+    # attention_doc.hip
+    "pto_attn_doc_fwd": [_VP] * 6 + [_I] * 5 + [_F, _VP],
+    "pto_attn_doc_bwd": [_VP] * 12 + [_I] * 5 + [_F, _VP],
     # pool.hip
     "pto_maxpool3s2_fwd": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     "pto_maxpool3s2_bwd": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
