@@ -25,6 +25,33 @@
 //     the Hq/Hkv query heads of its kv head and every query tile at or after its keys;
 //     S = Q.K^T, dP = dO.V^T, dV^T += dO^T.P, dK^T += Q^T.dS.  Deterministic, no atomics.
 //   Causal workgroups run heaviest-first (the block index is the slowest grid index).
+//
+// Document mask for packed-sequence training (pto_attn_doc_fwd / pto_attn_doc_bwd).  The two
+// 4-wave backward passes are written once, as bodies templated on kDoc (dq_pass, dkdv_pass); the
+// plain and the document kernels are thin wrappers around them.  Without kDoc every bound below is
+// a compile-time 0 / false; the document kernels are always causal (`causal` is the literal 1).
+// The wrappers declare the LDS arrays and hand them in: as static arrays of the inlined body they
+// cost the document dK/dV kernel two more registers (one more allocation granule).
+// The two forward kernels stay separate texts.  Merged the same way (the operand schedule as one
+// more template parameter) the document forward kept its registers and instruction counts but ran
+// 2 % slower at S = 8192, and the plain one 0.8 % (profiles/attn_merge/README.md); as kernels of
+// their own both compile to the instructions they had.  An edit to one forward's MFMA chains, mask
+// or softmax has to be made in the other: tests/test_attention_doc_gpu.py holds them bit-identical
+// with one document.
+// Mask: query i sees key j iff doc_start[b, i] <= j <= i, equivalently j <= i < doc_end[b, j].
+// doc_start [B, S] int32 is the index of the first token of token i's document, doc_end [B, S]
+// one past its last token; both are non-decreasing along S.  So
+//   * a wave's smallest / largest bound are the values at its first / last row (two wave-uniform
+//     loads), and the per-element bound is a per-lane scalar: doc_start[query on the lane] in the
+//     forward and dQ passes, doc_end[key on the lane] in the dK/dV pass;
+//   * the bound is applied only on tiles that straddle a boundary for the wave (wave-uniform
+//     test, like `diag` for the causal mask);
+//   * tiles no row of the workgroup can see are never loaded: a forward / dQ query block starts
+//     at key tile doc_start[first row of the block] / BN, and a dK/dV key block stops at query
+//     tile ceil(doc_end[last key of the block] / QT).
+// With doc_start == 0 (doc_end == S) every document kernel runs the plain kernel's operations in
+// its order: bit-identical outputs.  The bounds are clamped to the block's causal range before
+// they become tile indices, so no value in doc_start / doc_end can move a load out of the tensors.
 #include "attention_common.h"
 
 extern "C" int pto_attn_dq_pipe(const void* q, const void* k, const void* v, const void* o, const void* dout,
@@ -157,6 +184,152 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(const bf16_t* __restric
         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
           for (int dt = 0; dt < NDT; ++dt) oacc[dt] = mfma(vv[s2][dt], pb[s2], oacc[dt]);
+      }
+    }
+    if (more) {
+      u32x4* nk = smem + (cur ^ 1) * 2 * BN * CH;
+      ks.store(nk, tid);
+      vs.store(nk + BN * CH, tid);
+    }
+    __syncthreads();
+  }
+  l += __shfl_xor(l, 32);
+  const float inv = 1.f / l;
+  store_rows_T(oacc, inv, smem + w * 32 * CH, lane, o + ((size_t)b * S + q0w) * qstride + (size_t)hq * D, qstride);
+  if (h == 0) lse2[((size_t)b * Hq + hq) * S + qme] = m2 + log2f(l);
+}
+
+// ------------------------------------------------------- forward, document mask
+// attn_fwd_kernel with the bounds (see the top of the file for why it is not one body with it).
+// Differences: the tile loop starts at t0, the `kv0 < lomax` mask, the `msub` guard, and K / V
+// operands fetched one half / one k-step at a time.
+__global__ __launch_bounds__(NT, 2) void attn_doc_fwd_kernel(const bf16_t* __restrict__ q,
+                                                             const bf16_t* __restrict__ k,
+                                                             const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
+                                                             float* __restrict__ lse2,
+                                                             const int* __restrict__ doc_start, int B, int S, int Hq,
+                                                             int Hkv, float c) {
+  __shared__ u32x4 smem[4 * BN * CH];  // K0 V0 K1 V1 (64 KB)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, r = lane & 31;
+  int qblk, b, hq, hk;
+  block_coords(S, B, Hq, Hkv, 1, qblk, b, hq, hk);
+  const int q0w = qblk * BM + w * 32;
+  const size_t qstride = (size_t)Hq * D, kvstride = (size_t)Hkv * D;
+
+  bf16x8 qf[NDS];
+  {
+    const bf16_t* qrow = q + ((size_t)b * S + q0w + r) * qstride + (size_t)hq * D + 8 * h;
+#pragma unroll
+    for (int s = 0; s < NDS; ++s) qf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(qrow + 16 * s));
+  }
+  const bf16_t* kb = k + (size_t)b * S * kvstride + (size_t)hk * D;
+  const bf16_t* vb = v + (size_t)b * S * kvstride + (size_t)hk * D;
+  const int qme = q0w + r;
+  const int* ds = doc_start + (size_t)b * S;
+  const int lome = ds[qme];                  // first visible key of this lane's query
+  const int lomax = uniform(ds[q0w + 31]);   // the wave's largest bound (its last row's)
+  // first tile any row of the block sees, clamped into the block's causal range
+  const int t0 = min(max(uniform(ds[qblk * BM]), 0), qblk * BM) / BN;
+  const int ntiles = (qblk * BM + BM) / BN;
+
+  Stage<BN> ks, vs;
+  ks.load(kb + (size_t)t0 * BN * kvstride, kvstride, tid);
+  vs.load(vb + (size_t)t0 * BN * kvstride, kvstride, tid);
+  ks.store(smem, tid);
+  vs.store(smem + BN * CH, tid);
+  __syncthreads();
+
+  f32x16 oacc[NDT];
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) oacc[dt] = zero16();
+  float m2 = -INFINITY, l = 0.f;
+
+  for (int t = t0; t < ntiles; ++t) {
+    const int cur = (t - t0) & 1;
+    const u32x4* Ks = smem + cur * 2 * BN * CH;
+    const u32x4* Vs = Ks + BN * CH;
+    const int kv0 = t * BN;
+    const bool more = t + 1 < ntiles;
+    // No per-wave skip of wholly masked tiles (above the diagonal, or before every document of
+    // the wave): a branch around the accumulators makes the compiler shuttle them through AGPRs.
+    f32x16 sacc[2];
+    {
+      // S^T = K . Q^T, one 32-key half at a time (the plain forward keeps all 16 K row operands
+      // in flight; with the bounds live as well that spills at two workgroups per CU).  Each
+      // half's MFMA chain runs in the plain forward's order.
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        bf16x8 a[NDS];
+#pragma unroll
+        for (int s = 0; s < NDS; ++s) a[s] = row_frag(Ks, 32 * kt + r, 2 * s + h);
+        __builtin_amdgcn_sched_barrier(0);
+        sacc[kt] = zero16();
+#pragma unroll
+        for (int s = 0; s < NDS; ++s) sacc[kt] = mfma(a[s], qf[s], sacc[kt]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (more) {  // next tile's global loads fly under the softmax and P.V
+      ks.load(kb + (size_t)(t + 1) * BN * kvstride, kvstride, tid);
+      vs.load(vb + (size_t)(t + 1) * BN * kvstride, kvstride, tid);
+    }
+    {
+      if (kv0 + BN - 1 > q0w) {
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (kv0 + kt * 32 + acc_row(i, h) > qme) sacc[kt][i] = -INFINITY;
+      }
+      if (kv0 < lomax) {  // some row of the wave starts its document after this tile's first key
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (kv0 + kt * 32 + acc_row(i, h) < lome) sacc[kt][i] = -INFINITY;
+      }
+      float mx = sacc[0][0];
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kt][i]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mnew = fmaxf(m2, mx * c);
+      // The plain forward relies on a wholly masked tile never being a row's first tile, so that
+      // its running max is finite.  Here a wave's later rows can belong to a document that starts
+      // after the block's first processed tile: their first tiles are all -inf, m2 = mnew = -inf,
+      // and exp2(m2 - mnew) would be NaN.  Subtract 0 instead of -inf in both exponentials (a
+      // select, no branch around the accumulators): alpha = exp2(-inf) = 0 and p = exp2(-inf) = 0,
+      // so a row with no visible key yet keeps m2 = -inf, l = 0 and O = 0.  With a finite max the
+      // values are the plain forward's.
+      const float msub = mnew == -INFINITY ? 0.f : mnew;
+      const float alpha = __builtin_amdgcn_exp2f(m2 - msub);
+      m2 = mnew;
+      float rs = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kt][i], c, -msub));
+          sacc[kt][i] = p;
+          rs += p;
+        }
+      l = fmaf(l, alpha, rs);
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) oacc[dt] *= alpha;
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {  // one k-step's V operands at a time (registers)
+          bf16x8 vv[NDT];
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) vv[dt] = tr_frag(Vs, kt * 32 + 16 * s2, dt * 32, lane);
+          const bf16x8 pb = acc_frag(sacc[kt], s2);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int dt = 0; dt < NDT; ++dt) oacc[dt] = mfma(vv[dt], pb, oacc[dt]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
     }
     if (more) {
@@ -323,12 +496,13 @@ __global__ __launch_bounds__(NT8, 1) void attn_fwd8_kernel(const bf16_t* __restr
 }
 
 // ------------------------------------------------------------------- backward pass 1: dQ
-__global__ __launch_bounds__(NT, 1) void attn_bwd_dq_kernel(
-    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-    const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout, const float* __restrict__ lse2,
-    float* __restrict__ delta, bf16_t* __restrict__ dq, int B, int S, int Hq, int Hkv, float c, float scale,
-    int causal) {
-  __shared__ u32x4 smem[4 * BN * CH];
+template <bool kDoc>
+__device__ __forceinline__ void dq_pass(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                        const bf16_t* __restrict__ v, const bf16_t* __restrict__ o,
+                                        const bf16_t* __restrict__ dout, const float* __restrict__ lse2,
+                                        float* __restrict__ delta, bf16_t* __restrict__ dq,
+                                        const int* __restrict__ doc_start, int B, int S, int Hq, int Hkv, float c,
+                                        float scale, int causal, u32x4* smem) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, r = lane & 31;
   int qblk, b, hq, hk;
   block_coords(S, B, Hq, Hkv, causal, qblk, b, hq, hk);
@@ -362,10 +536,14 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dq_kernel(
 
   const bf16_t* kb = k + (size_t)b * S * kvstride + (size_t)hk * D;
   const bf16_t* vb = v + (size_t)b * S * kvstride + (size_t)hk * D;
+  const int* ds = kDoc ? doc_start + (size_t)b * S : nullptr;  // the forward's bounds
+  const int lome = kDoc ? ds[qme] : 0;
+  const int lomax = kDoc ? uniform(ds[q0w + 31]) : 0;
+  const int t0 = kDoc ? min(max(uniform(ds[qblk * BM]), 0), qblk * BM) / BN : 0;
   const int ntiles = causal ? (qblk * BM + BM) / BN : S / BN;
   Stage<BN> ks, vs;
-  ks.load(kb, kvstride, tid);
-  vs.load(vb, kvstride, tid);
+  ks.load(kb + (size_t)t0 * BN * kvstride, kvstride, tid);
+  vs.load(vb + (size_t)t0 * BN * kvstride, kvstride, tid);
   ks.store(smem, tid);
   vs.store(smem + BN * CH, tid);
   __syncthreads();
@@ -374,14 +552,15 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dq_kernel(
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) dacc[dt] = zero16();
 
-  for (int t = 0; t < ntiles; ++t) {
-    const int cur = t & 1;
+  for (int t = t0; t < ntiles; ++t) {
+    const int cur = (t - t0) & 1;
     const u32x4* Ks = smem + cur * 2 * BN * CH;
     const u32x4* Vs = Ks + BN * CH;
     const int kv0 = t * BN;
     const bool more = t + 1 < ntiles;
     {  // no per-wave skip of masked tiles (see the forward)
       const bool diag = causal && kv0 + BN - 1 > q0w;
+      const bool edge = kDoc && kv0 < lomax;  // a document of the wave starts after this tile's first key
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         f32x16 sa = zero16(), pa = zero16();
@@ -407,6 +586,7 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dq_kernel(
         for (int i = 0; i < 16; ++i) {
           float p = __builtin_amdgcn_exp2f(fmaf(sa[i], c, -lq));
           if (diag && kv0 + kt * 32 + acc_row(i, h) > qme) p = 0.f;
+          if (edge && kv0 + kt * 32 + acc_row(i, h) < lome) p = 0.f;  // the saved lse2 excludes it
           sa[i] = p * (pa[i] - dl);
         }
         bf16x8 db[2], kk[2][NDT];
@@ -433,17 +613,36 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dq_kernel(
   store_rows_T(dacc, scale, smem + w * 32 * CH, lane, dq + ((size_t)b * S + q0w) * qstride + (size_t)hq * D, qstride);
 }
 
-// -------------------------------------------------------------- backward pass 2: dK, dV
-__global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(
+__global__ __launch_bounds__(NT, 1) void attn_bwd_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-    const bf16_t* __restrict__ dout, const float* __restrict__ lse2, const float* __restrict__ delta,
-    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int B, int S, int Hq, int Hkv, float c, float scale,
+    const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout, const float* __restrict__ lse2,
+    float* __restrict__ delta, bf16_t* __restrict__ dq, int B, int S, int Hq, int Hkv, float c, float scale,
     int causal) {
-  __shared__ u32x4 smem[4 * QT * CH];  // Q0 dO0 Q1 dO1 (32 KB); reused for the dK/dV epilogue
-  __shared__ float4 stat[2][2][QT / 4];  // [buf][lse2 | delta][32 rows]
+  __shared__ u32x4 smem[4 * BN * CH];  // K0 V0 K1 V1 (64 KB)
+  dq_pass<false>(q, k, v, o, dout, lse2, delta, dq, nullptr, B, S, Hq, Hkv, c, scale, causal, smem);
+}
+
+__global__ __launch_bounds__(NT, 1) void attn_doc_dq_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout, const float* __restrict__ lse2,
+    float* __restrict__ delta, bf16_t* __restrict__ dq, const int* __restrict__ doc_start, int B, int S, int Hq,
+    int Hkv, float c, float scale) {
+  __shared__ u32x4 smem[4 * BN * CH];  // K0 V0 K1 V1 (64 KB)
+  dq_pass<true>(q, k, v, o, dout, lse2, delta, dq, doc_start, B, S, Hq, Hkv, c, scale, 1, smem);
+}
+
+// -------------------------------------------------------------- backward pass 2: dK, dV
+template <bool kDoc>
+__device__ __forceinline__ void dkdv_pass(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                          const bf16_t* __restrict__ v, const bf16_t* __restrict__ dout,
+                                          const float* __restrict__ lse2, const float* __restrict__ delta,
+                                          bf16_t* __restrict__ dk, bf16_t* __restrict__ dv,
+                                          const int* __restrict__ doc_end, int B, int S, int Hq, int Hkv, float c,
+                                          float scale, int causal, u32x4* smem, float4 (*stat)[2][QT / 4]) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, r = lane & 31;
   // key block slowest in the launch order: under the causal mask kblk 0 (the most query tiles)
-  // is dispatched first, so the light blocks fill in behind the heavy ones
+  // is dispatched first, so the light blocks fill in behind the heavy ones (with documents a
+  // block's weight depends on where its last key's document ends, not on kblk alone)
   const int kblk = (int)blockIdx.x / (B * Hkv), bh = (int)blockIdx.x % (B * Hkv);
   const int b = bh / Hkv, hk = bh % Hkv, G = Hq / Hkv;
   const int k0w = kblk * BK + w * 32, kme = k0w + r;
@@ -458,8 +657,13 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(
       vf[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(v + off + 16 * s));
     }
   }
+  const int* de = kDoc ? doc_end + (size_t)b * S : nullptr;
+  const int hime = kDoc ? de[kme] : 0;            // one past the last query that sees this lane's key
+  const int himin = kDoc ? uniform(de[k0w]) : 0;  // the wave's smallest bound (its first key's)
   const int qt0 = causal ? (kblk * BK) / QT : 0;
-  const int nqt = S / QT - qt0;  // query tiles per head
+  // one past the last query tile any key of the block is seen from, clamped to [qt0 + 1, S / QT]
+  const int qtend = kDoc ? min(max((uniform(de[kblk * BK + BK - 1]) + QT - 1) / QT, qt0 + 1), S / QT) : S / QT;
+  const int nqt = qtend - qt0;  // query tiles per head
   const int ntiles = G * nqt;
 
   auto tile_ptrs = [&](int t, const bf16_t*& qp, const bf16_t*& dp, size_t& srow) {
@@ -518,6 +722,7 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(
     if (more) load(t + 1);
     {
       const bool diag = causal && k0w + 31 > q0;
+      const bool edge = kDoc && q0 + QT > himin;  // a document of the wave ends before this tile's last query
       // rows (queries) of register group g: 8g + 4h + 0..3 -> one float4 of lse2 / delta
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -529,6 +734,7 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(
           const int i = 4 * g + e;
           float p = __builtin_amdgcn_exp2f(fmaf(sa[i], c, -Lv[e]));
           if (diag && kme > q0 + 8 * g + 4 * h + e) p = 0.f;
+          if (edge && q0 + 8 * g + 4 * h + e >= hime) p = 0.f;  // a query of a later document
           sa[i] = p;
           pa[i] = p * (pa[i] - Dv[e]);
         }
@@ -564,7 +770,28 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(
   store_rows_T(dka, scale, smem + w * 32 * CH, lane, dk + off, kvstride);
 }
 
+__global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ dout, const float* __restrict__ lse2, const float* __restrict__ delta,
+    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int B, int S, int Hq, int Hkv, float c, float scale,
+    int causal) {
+  __shared__ u32x4 smem[4 * QT * CH];  // Q0 dO0 Q1 dO1 (32 KB); reused for the dK/dV epilogue
+  __shared__ float4 stat[2][2][QT / 4];  // [buf][lse2 | delta][32 rows]
+  dkdv_pass<false>(q, k, v, dout, lse2, delta, dk, dv, nullptr, B, S, Hq, Hkv, c, scale, causal, smem, stat);
+}
+
+__global__ __launch_bounds__(NT, 1) void attn_doc_dkdv_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+    const bf16_t* __restrict__ dout, const float* __restrict__ lse2, const float* __restrict__ delta,
+    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, const int* __restrict__ doc_end, int B, int S, int Hq,
+    int Hkv, float c, float scale) {
+  __shared__ u32x4 smem[4 * QT * CH];  // Q0 dO0 Q1 dO1 (32 KB); reused for the dK/dV epilogue
+  __shared__ float4 stat[2][2][QT / 4];  // [buf][lse2 | delta][32 rows]
+  dkdv_pass<true>(q, k, v, dout, lse2, delta, dk, dv, doc_end, B, S, Hq, Hkv, c, scale, 1, smem, stat);
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+bool aligned4(const void* p) { return p != nullptr && ((uintptr_t)p & 3u) == 0; }  // doc_start / doc_end
 
 // Pass selection.  Default build: forward 10 (the 8-wave forward with LDS-DMA K/V staging, S % 256
 // == 0; the 4-wave attn_fwd_kernel otherwise), dQ 9 and dK/dV 8 (the software-pipelined passes of
@@ -668,6 +895,42 @@ int pto_attn_bwd(const void* q, const void* k, const void* v, const void* o, con
     hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3((S / BK) * B * Hkv), dim3(NT), 0, (hipStream_t)stream,
                        (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse2,
                        (const float*)delta, (bf16_t*)dk, (bf16_t*)dv, B, S, Hq, Hkv, c, scale, causal);
+  return (int)hipGetLastError();
+}
+
+// pto_attn_fwd under the document mask: the same tensors (q [B,S,Hq,128], k/v [B,S,Hkv,128], o
+// [B,S,Hq,128] bf16 contiguous; lse2 [B,Hq,S] f32, log2 units; S a multiple of 128, Hq a multiple
+// of Hkv) plus doc_start [B,S] int32.  Always causal, always the 4-wave document kernel.
+int pto_attn_doc_fwd(const void* q, const void* k, const void* v, void* o, float* lse2, const int* doc_start, int B,
+                     int S, int Hq, int Hkv, int Dh, float scale, void* stream) {
+  if (check_shapes(B, S, Hq, Hkv, Dh)) return -1;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(lse2) || !aligned4(doc_start))
+    return -2;
+  const float c = scale * 1.4426950408889634f;
+  hipLaunchKernelGGL(attn_doc_fwd_kernel, dim3((S / BM) * B * Hq), dim3(NT), 0, (hipStream_t)stream,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2, doc_start, B, S, Hq, Hkv,
+                     c);
+  return (int)hipGetLastError();
+}
+
+// pto_attn_bwd under the document mask: the same tensors (dq [B,S,Hq,128], dk/dv [B,S,Hkv,128]
+// bf16; delta [B,Hq,S] f32 scratch, rowsum(dO * O)) plus doc_start / doc_end [B,S] int32.  Two
+// launches, deterministic, no atomics.
+int pto_attn_doc_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse2,
+                     float* delta, void* dq, void* dk, void* dv, const int* doc_start, const int* doc_end, int B,
+                     int S, int Hq, int Hkv, int Dh, float scale, void* stream) {
+  if (check_shapes(B, S, Hq, Hkv, Dh)) return -1;
+  const void* ps[] = {q, k, v, o, dout, lse2, delta, dq, dk, dv};
+  for (const void* p : ps)
+    if (!aligned16(p)) return -2;
+  if (!aligned4(doc_start) || !aligned4(doc_end)) return -2;
+  const float c = scale * 1.4426950408889634f;
+  hipLaunchKernelGGL(attn_doc_dq_kernel, dim3((S / BM) * B * Hq), dim3(NT), 0, (hipStream_t)stream,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout,
+                     lse2, delta, (bf16_t*)dq, doc_start, B, S, Hq, Hkv, c, scale);
+  hipLaunchKernelGGL(attn_doc_dkdv_kernel, dim3((S / BK) * B * Hkv), dim3(NT), 0, (hipStream_t)stream,
+                     (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout, lse2,
+                     (const float*)delta, (bf16_t*)dk, (bf16_t*)dv, doc_end, B, S, Hq, Hkv, c, scale);
   return (int)hipGetLastError();
 }
 

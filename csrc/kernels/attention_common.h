@@ -1,6 +1,6 @@
-// Shared pieces of the flash-attention kernels (attention.hip, attention_bwd_pipe.hip): operand
-// types, the MFMA / LDS-image helpers, tile staging and the launch-order map.  See attention.hip
-// for the layout and MFMA plan.
+// Shared pieces of the flash-attention kernels (attention.hip, which also holds the document-masked
+// kernels, and attention_bwd_pipe.hip): operand types, the MFMA / LDS-image helpers, tile staging
+// and the launch-order map.  See attention.hip for the layout and MFMA plan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -110,6 +110,9 @@ __device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >
 
 __device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
 
+// a value every lane of the wave holds, moved to a scalar register
+__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
 // Stage a [ROWS][128] bf16 tile (rows ROWS apart in global by `stride` elements) into the
 // XOR image: each thread moves ROWS*16/NT 16-byte chunks.
 template <int ROWS, int NTH = NT>
@@ -179,9 +182,9 @@ __device__ __forceinline__ void glds_dword_asm(const float* src, float* lds_dst)
 }
 
 // Write a wave's 32 x 128 transposed accumulator (acc[dt] reg i = [d = dt*32 + acc_row(i,h)]
-// [col = lane & 31]) as rows [col][d] bf16 to global via the wave's LDS region (8 KB).
-__device__ __forceinline__ void store_rows_T(const f32x16 (&acc)[NDT], float scale, u32x4* stage, int lane,
-                                             bf16_t* out, size_t row_stride) {
+// [col = lane & 31]) as rows [col][d] bf16 to global via the wave's LDS region (8 KB): the two
+// halves, then the two forms of the hand-off between them.
+__device__ __forceinline__ void rows_T_to_lds(const f32x16 (&acc)[NDT], float scale, u32x4* stage, int lane) {
   const int c = lane & 31, h = lane >> 5;
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt)
@@ -193,7 +196,8 @@ __device__ __forceinline__ void store_rows_T(const f32x16 (&acc)[NDT], float sca
       w.y = pk_bf16(acc[dt][4 * g + 2] * scale, acc[dt][4 * g + 3] * scale);
       *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(stage + xo(c, d0 >> 3)) + (d0 & 7) * 2) = w;
     }
-  __syncthreads();  // every wave calls this together (after its tile loop)
+}
+__device__ __forceinline__ void rows_from_lds(const u32x4* stage, int lane, bf16_t* out, size_t row_stride) {
 #pragma unroll
   for (int i = 0; i < 32 * CH / 64; ++i) {
     const int e = lane + 64 * i, row = e / CH, ch = e % CH;
@@ -201,30 +205,23 @@ __device__ __forceinline__ void store_rows_T(const f32x16 (&acc)[NDT], float sca
   }
 }
 
+__device__ __forceinline__ void store_rows_T(const f32x16 (&acc)[NDT], float scale, u32x4* stage, int lane,
+                                             bf16_t* out, size_t row_stride) {
+  rows_T_to_lds(acc, scale, stage, lane);
+  __syncthreads();  // every wave calls this together (after its tile loop)
+  rows_from_lds(stage, lane, out, row_stride);
+}
+
 // store_rows_T for a wave whose staging region no other wave touches any more (after the last
 // tile's barrier): the hand-off from this wave's LDS writes to its own reads needs no block
 // barrier (one wave's LDS operations complete in order)
 __device__ __forceinline__ void store_rows_T_wave(const f32x16 (&acc)[NDT], float scale, u32x4* stage, int lane,
                                                   bf16_t* out, size_t row_stride) {
-  const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = dt * 32 + 8 * g + 4 * h;
-      u32x2 w;
-      w.x = pk_bf16(acc[dt][4 * g + 0] * scale, acc[dt][4 * g + 1] * scale);
-      w.y = pk_bf16(acc[dt][4 * g + 2] * scale, acc[dt][4 * g + 3] * scale);
-      *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(stage + xo(c, d0 >> 3)) + (d0 & 7) * 2) = w;
-    }
+  rows_T_to_lds(acc, scale, stage, lane);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-  for (int i = 0; i < 32 * CH / 64; ++i) {
-    const int e = lane + 64 * i, row = e / CH, ch = e % CH;
-    *reinterpret_cast<u32x4*>(out + (size_t)row * row_stride + ch * 8) = stage[xo(row, ch)];
-  }
+  rows_from_lds(stage, lane, out, row_stride);
 }
 
 // Forward / dQ workgroup -> (query block, batch, q head, kv head).  The query block is the

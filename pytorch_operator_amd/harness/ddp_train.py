@@ -102,8 +102,8 @@ def parse_args(argv=None):
                         "device inside the optimizer (csrc/kernels/gradclip.hip)")
     p.add_argument("--doc-len-mean", type=int, default=0,
                    help="Llama: pack documents into each sequence -- every position becomes the end-of-text "
-                        "token with probability 1/N, attention stays inside each document "
-                        "(csrc/kernels/attention_doc.hip) and the target after an end-of-text token is "
+                        "token with probability 1/N, attention stays inside each document (the document "
+                        "kernels of csrc/kernels/attention.hip) and the target after an end-of-text token is "
                         "ignored; 0 = off (one document per sequence)")
     p.add_argument("--eos-id", type=int, default=None,
                    help="end-of-text token id for --doc-len-mean (default: the last vocabulary id)")

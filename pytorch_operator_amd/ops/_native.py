@@ -46,15 +46,13 @@ def _sources():
 # Per-file compiler flags.  attention.hip: MFMAs in VGPR form -- its one-wave-per-SIMD dK/dV
 # kernels need more than the 256 architectural VGPRs, and with the default (AGPR-form)
 # accumulators the compiler moved them between AGPRs and VGPRs every tile (298 v_accvgpr_read +
-# 261 v_accvgpr_write in the kernel against 31 + 22 with VGPR form).
+# 261 v_accvgpr_write in the kernel against 31 + 22 with VGPR form).  Its document-masked kernels
+# are in the same file as the plain 4-wave ones they derive from, so they are built with the same flags.
 # attention_bwd_pipe.hip: VGPR form as well (its dK/dV accumulators are pinned in AGPRs by its
 # own asm MFMAs, so the compiler's MFMAs (S, dP) write VGPRs that the VALU reads directly), and
 # no SLP vectorisation: packed f32 VALU beside MFMAs costs more issue time than two scalar ops
 # (MI355X_MICROARCH.md, constants table).
-# attention_doc.hip: attention.hip's flags, so that the code its document-masked passes share with
-# the plain 4-wave passes is generated the same way (they are bit-identical with one document).
 _FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "attention_doc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
 
 
@@ -206,7 +204,7 @@ _SIGNATURES = {
     "pto_attn_set_variant": [_I],
     "pto_attn_set_dkdv_variant": [_I],
     "pto_attn_set_dq_variant": [_I],
-    # attention_doc.hip
+    # attention.hip, document mask
     "pto_attn_doc_fwd": [_VP] * 6 + [_I] * 5 + [_F, _VP],
     "pto_attn_doc_bwd": [_VP] * 12 + [_I] * 5 + [_F, _VP],
     # pool.hip

@@ -12,9 +12,11 @@ deterministic.  On CPU the same math runs in PyTorch (``attention_reference``); 
 with an unsupported shape raises instead of falling back silently.
 
 ``flash_attention(q, k, v, doc_start=ds)`` is the document mask of packed-sequence training
-(``csrc/kernels/attention_doc.hip``): ``ds`` [B, S] holds, per token, the index of the first token
-of its document, and query i sees key j iff ``ds[b, i] <= j <= i``.  ``doc_starts_from_tokens``
-builds it from an end-of-text id, ``validate_doc_start`` checks it where a batch is built.
+(the ``attn_doc_*`` kernels of ``attention.hip``, siblings of the plain 4-wave kernels; the two
+backward passes share one templated body each with them): ``ds`` [B, S] holds, per token, the
+index of the first token of its document, and query i sees key j iff ``ds[b, i] <= j <= i``.
+``doc_starts_from_tokens`` builds it from an end-of-text id, ``validate_doc_start`` checks it where
+a batch is built.
 """
 from __future__ import annotations
 
@@ -150,7 +152,7 @@ class _FlashAttention(torch.autograd.Function):
 
 
 class _FlashAttentionDoc(torch.autograd.Function):
-    """The document-masked passes (attention_doc.hip): doc_start / doc_end int32 [B, S]."""
+    """The document-masked passes (the attn_doc_* kernels of attention.hip): doc_start / doc_end int32 [B, S]."""
 
     @staticmethod
     def forward(ctx, q, k, v, doc_start, doc_end):

@@ -1,7 +1,7 @@
 """Document-masked attention for packed sequences, the parts that need no GPU: the doc_start
 helpers, the fp32 masked reference and the Llama model against running each document on its own,
 the worker's --doc-len-mean option, and the register budget of the three HIP kernels
-(csrc/kernels/attention_doc.hip) in the built library."""
+(the attn_doc_* kernels of csrc/kernels/attention.hip) in the built library."""
 import json
 import math
 import os

@@ -1,4 +1,5 @@
-"""The document-masked HIP flash attention (csrc/kernels/attention_doc.hip) on the GPU: numerics
+"""The document-masked HIP flash attention (the attn_doc_* kernels of csrc/kernels/attention.hip)
+on the GPU: numerics
 against the fp32 masked reference with the dense-mask SDPA's own bf16 error as the yardstick
 (test_attention_gpu.py's), bit-identity with the plain 4-wave passes when there is one document,
 bit-for-bit independence of the documents, and the Llama model's dispatch."""
@@ -116,8 +117,9 @@ def test_doc_backward_matches_fp32_masked_reference(shape, layout):
 @pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_one_document_is_bit_identical_to_the_plain_passes(shape, dtype):
-    """doc_start all zeros: the same operations in the same order as forward 4, dQ 4 and dK/dV 1,
-    only the bounds differ."""
+    """doc_start all zeros: the same operations in the same order as forward 4, dQ 4 and dK/dV 1
+    (dQ and dK/dV: the same templated bodies; the forward: a sibling kernel whose text must follow
+    the plain forward's), only the bounds and the forward's operand schedule differ."""
     from pytorch_operator_amd.ops import _native
     from pytorch_operator_amd.ops.attention import flash_attention
     lib = _native.load()

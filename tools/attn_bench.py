@@ -9,11 +9,11 @@ causal half: fwd 2 products, bwd 5 products (the HIP backward does 7: see attent
 
 --doc-len-mean N packs documents of mean length N into every sequence (boundaries drawn per
 position with probability 1/N from a fixed seed) and also times, on the same tensors, the HIP
-document path (attention_doc.hip: "hip_doc"), that path with one document per sequence
-("hip_doc_one": the price of its plain 4-wave passes) and SDPA with the dense boolean mask
-("sdpa_doc").  "visited_tile_fraction" is the share of the causal (query block, key tile) pairs
-the document path's forward / dQ passes visit, and of the (key block, query tile) pairs its dK/dV
-pass visits, counted on the host from doc_start.
+document path (the attn_doc_* kernels of attention.hip: "hip_doc"), that path with one document
+per sequence ("hip_doc_one": the price of its plain 4-wave passes) and SDPA with the dense boolean
+mask ("sdpa_doc").  "visited_tile_fraction" is the share of the causal (query block, key tile)
+pairs the document path's forward / dQ passes visit, and of the (key block, query tile) pairs its
+dK/dV pass visits, counted on the host from doc_start.
 """
 import argparse
 import json
