@@ -73,6 +73,12 @@ def parse_args(argv=None):
     p.add_argument("--linear-bwd", choices=["tn", "autograd"], default="tn",
                    help="Llama projections: backward GEMMs with K-contiguous (transposed-copy) operands, "
                         "or autograd's dy.W / dy^T.x layouts")
+    p.add_argument("--linear-dtype", choices=["bf16", "fp8"], default="bf16",
+                   help="Llama, --dtype bf16: fp8 runs the wqkv / wo / w13 / w2 GEMMs (forward and both backward "
+                        "ones) in per-tensor-scaled OCP FP8 (ops/fp8.py, csrc/kernels/fp8_cast.hip); the lm head "
+                        "and the embedding stay bf16")
+    p.add_argument("--fp8-grad-format", choices=["e5m2", "e4m3"], default="e5m2",
+                   help="--linear-dtype fp8: format of the output gradients (activations and weights are e4m3)")
     p.add_argument("--opt-overlap", choices=["on", "off"], default="off",
                    help="Llama (master weights): AdamW updates on a side stream, overlapped with the next "
                         "forward (each module waits only for its own parameters' updates); measured neutral "
@@ -110,7 +116,10 @@ def parse_args(argv=None):
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.linear_dtype == "fp8" and not (args.model.startswith("llama") and args.dtype == "bf16"):
+        p.error("--linear-dtype fp8 is for the Llama models with --dtype bf16")
+    return args
 
 
 def use_zero(args, device, world: int) -> bool:
@@ -148,7 +157,8 @@ def build(args, device, world: int = 1):
         return model, opt
     from ..models.llama import CONFIGS, Attention, Llama, RMSNorm, TNLinear
     Attention.impl = args.attn
-    TNLinear.impl = args.linear_bwd
+    TNLinear.impl = "fp8" if args.linear_dtype == "fp8" else args.linear_bwd
+    TNLinear.fp8_grad_format = args.fp8_grad_format
     RMSNorm.fuse_residual = args.residual_norm == "fused"
     with torch.device(device):
         model = Llama(CONFIGS[args.model], checkpoint_layers=args.grad_checkpoint)
@@ -435,6 +445,8 @@ def main(argv=None) -> int:
     if is_llama:
         res.update(attn=args.attn, residual_norm=args.residual_norm, linear_bwd=args.linear_bwd,
                    opt_overlap=args.opt_overlap if res["master_weights"] and not zero else None)
+    if args.linear_dtype == "fp8":  # (the default's result line keeps its keys)
+        res.update(linear_dtype=args.linear_dtype, grad_format=args.fp8_grad_format)
     if is_llama and doc_start is not None:
         res.update(doc_len_mean=args.doc_len_mean, docs_per_seq=round(docs_per_seq, 2), attn_mask="document")
     if tuning.get("mode") == "tune" and rank == 0:

@@ -107,14 +107,19 @@ class RMSNorm(nn.Module):
 
 class TNLinear(nn.Linear):
     """Bias-free projection whose backward GEMMs take K-contiguous operands (``ops.llm.linear_tn``)
-    when ``impl == "tn"``; ``"autograd"`` is the plain ``nn.Linear`` backward (A/B)."""
+    when ``impl == "tn"``; ``"autograd"`` is the plain ``nn.Linear`` backward (A/B); ``"fp8"`` runs the
+    forward and both backward GEMMs in per-tensor-scaled FP8 (``ops.fp8.fp8_linear``, GPU and CPU)."""
 
     impl = "tn"
+    fp8_grad_format = "e5m2"  # impl "fp8": the output gradient's format (x and w are e4m3)
 
     def __init__(self, fin: int, fout: int):
         super().__init__(fin, fout, bias=False)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.impl == "fp8":
+            from ..ops import fp8
+            return fp8.fp8_linear(x, self.weight, self.fp8_grad_format)
         if self.impl == "tn" and x.is_cuda:
             from ..ops.llm import linear_tn
             return linear_tn(x, self.weight)

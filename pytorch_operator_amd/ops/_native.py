@@ -194,6 +194,9 @@ _SIGNATURES = {
     # gradclip.hip
     "pto_grad_sumsq": [_VP, _L, _I, _F, _VP, _L, _VP],
     "pto_grad_sumsq_finish": [_VP, _L, _VP, _VP],
+    # fp8_cast.hip
+    "pto_fp8_amax": [_VP, _L, _L, _VP, _L, _VP],
+    "pto_fp8_cast": [_VP, _L, _L, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP],
     # batchnorm.hip
     "pto_bn_plan": [_L, _I, ctypes.POINTER(_I)],
     "pto_bn_fwd_train": [_VP] * 12 + [_L, _I, _I, _I, _F, _F, _I, _I, _VP, _VP],
@@ -221,7 +224,7 @@ _SIGNATURES = {
     "pto_device_prewarm": [_I, _VP, _VP],
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
-             "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I]}
+             "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L]}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 
