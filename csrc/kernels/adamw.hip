@@ -23,18 +23,26 @@ struct AdamArgs {
   float lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, gscale;
 };
 
+// Round to nearest even.  A NaN stays a NaN (quiet, same sign): the rounding carry would run out
+// of an all-ones mantissa into the exponent and sign (0xffffffff -> +0.0, 0x7fffffff -> -0.0).
 __device__ __forceinline__ uint32_t bf16_rne(float f) {
   const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
+// The fused multiply-adds are spelled out and the compiler's own contraction is off: left to
+// choose, it fused different products in different instantiations (and in different lanes of one
+// float4), so the clipped kernel with a coefficient of exactly 1 did not give the unclipped
+// kernel's bits.  Now every instantiation and lane rounds alike.
 __device__ __forceinline__ float adam1(float& p, float& m, float& v, float g, const AdamArgs& a) {
+#pragma clang fp contract(off)
   g *= a.gscale;  // 1, or the data-parallel 1/W of an unscaled gradient sum (exact for W = 2^k)
   p *= 1.f - a.lr * a.wd;
-  m = a.b1 * m + (1.f - a.b1) * g;
-  v = a.b2 * v + (1.f - a.b2) * g * g;
+  m = fmaf(a.b1, m, (1.f - a.b1) * g);
+  v = fmaf(a.b2, v, (1.f - a.b2) * g * g);
   // torch: denom = sqrt(v) / sqrt(bc2) + eps ; p -= (lr / bc1) * m / denom
-  p -= a.lr * a.inv_bc1 * m / (sqrtf(v) * a.inv_sqrt_bc2 + a.eps);
+  p -= a.lr * a.inv_bc1 * m / fmaf(sqrtf(v), a.inv_sqrt_bc2, a.eps);
   return p;
 }
 

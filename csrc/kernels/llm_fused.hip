@@ -34,8 +34,11 @@ struct V8 {
 };
 
 __device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) {  // round to nearest even (inputs are finite)
+// Round to nearest even.  A NaN stays a NaN (quiet, same sign): the rounding carry would run out
+// of an all-ones mantissa into the exponent and sign (0xffffffff -> +0.0, 0x7fffffff -> -0.0).
+__device__ __forceinline__ uint16_t f2bf(float f) {
   const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(kT) void swiglu_packed_bwd_kernel(const T* __restri
     for (int i = 0; i < 8; ++i) {
       const float sg = sigmoid(av.v[i]);
       oa.v[i] = gv.v[i] * bv.v[i] * sg * (1.f + av.v[i] * (1.f - sg));
-      ob.v[i] = gv.v[i] * av.v[i] * sg;
+      ob.v[i] = gv.v[i] * (av.v[i] * sg);  // silu first: dy * a can overflow where silu(a) is -0
     }
     Vec<T>::store(dx + r * 2 * F + c, oa);
     Vec<T>::store(dx + r * 2 * F + F + c, ob);
@@ -222,7 +225,7 @@ __global__ __launch_bounds__(kT) void swiglu_bwd_kernel(const T* __restrict__ dy
       for (int i = 0; i < 8; ++i) {
         const float sg = sigmoid(av.v[i]);
         oa.v[i] = gv.v[i] * bv.v[i] * sg * (1.f + av.v[i] * (1.f - sg));
-        ob.v[i] = gv.v[i] * av.v[i] * sg;
+        ob.v[i] = gv.v[i] * (av.v[i] * sg);  // silu first: dy * a can overflow where silu(a) is -0
       }
       Vec<T>::store(da + g * 8, oa);
       Vec<T>::store(db + g * 8, ob);
@@ -231,7 +234,7 @@ __global__ __launch_bounds__(kT) void swiglu_bwd_kernel(const T* __restrict__ dy
         const float gv = Vec<T>::load1(dy + i), av = Vec<T>::load1(a + i), bv = Vec<T>::load1(b + i);
         const float sg = sigmoid(av);
         Vec<T>::store1(da + i, gv * bv * sg * (1.f + av * (1.f - sg)));
-        Vec<T>::store1(db + i, gv * av * sg);
+        Vec<T>::store1(db + i, gv * (av * sg));
       }
     }
   }
@@ -258,10 +261,11 @@ __global__ __launch_bounds__(kX) void xent_fwd_kernel(const T* __restrict__ x, c
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, v.v[i]);
     const float mn = fmaxf(m, mx);
+    if (mn == -INFINITY) continue;  // nothing but -inf (masked columns) so far: (m, s) stays (-inf, 0)
     float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc += __expf(v.v[i] - mn);
-    s = s * __expf(m - mn) + acc;  // m = -inf on the first group: exp(-inf) = 0
+    s = s * __expf(m - mn) + acc;  // m = -inf on the first finite group: exp(-inf) = 0
     m = mn;
   }
   // wave, then block: combine (m, s) pairs
@@ -279,7 +283,7 @@ __global__ __launch_bounds__(kX) void xent_fwd_kernel(const T* __restrict__ x, c
 #pragma unroll
     for (int q = 1; q < kX / 64; ++q) {
       const float mn = fmaxf(M, sm[q]);
-      Ssum = Ssum * __expf(M - mn) + ss[q] * __expf(sm[q] - mn);
+      Ssum = (mn == -INFINITY) ? 0.f : Ssum * __expf(M - mn) + ss[q] * __expf(sm[q] - mn);
       M = mn;
     }
     const float lse = M + __logf(Ssum);

@@ -58,8 +58,11 @@ template <>
 __device__ __forceinline__ void st4<float>(float* p, const F4& r) {
   *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
 }
+// Round to nearest even.  A NaN stays a NaN (quiet, same sign): the rounding carry would run out
+// of an all-ones mantissa into the exponent and sign (0xffffffff -> +0.0, 0x7fffffff -> -0.0).
 __device__ __forceinline__ uint32_t bf16_rne(float f) {
   const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
   return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 template <>

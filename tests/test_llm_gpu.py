@@ -29,8 +29,20 @@ def test_rmsnorm_matches_reference(dtype, shape):
     tol = dict(rtol=1e-4, atol=1e-4) if dtype == torch.float32 else dict(rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(y.float(), yr, **tol)
     torch.testing.assert_close(x.grad.float(), xr.grad, **tol)
-    torch.testing.assert_close(w.grad, wr.grad, rtol=1e-3 if dtype == torch.float32 else 3e-2,
-                               atol=1e-3 if dtype == torch.float32 else 3e-1)
+    _assert_dw(w.grad, x.detach(), w.detach(), dy)
+
+
+def _assert_dw(dw, x, w, dy, stats_from=None):
+    """dw_j against fp64 of the values the backward kernel reads: |dw_j - dw64_j| <= 1e-5 *
+    sum_rows |dy x rstd|.  Both sides start from the same values and the kernel accumulates in
+    fp32 over <= 8 rows per block plus <= 32 column-sum slices: under 64 roundings, 3.8e-6."""
+    from llm_refs import FP32_E, rmsnorm_fp64, worst_ratio
+    D = x.shape[-1]
+    ref = rmsnorm_fp64(x.cpu().reshape(-1, D), w.cpu(), dy.cpu().reshape(-1, D), 1e-5,
+                       stats_from=None if stats_from is None else stats_from.reshape(-1, D))
+    ratio = worst_ratio(dw.cpu(), ref["dw"], FP32_E * ref["dwmag"])
+    print(f"dw worst error/bound {ratio:.3f}")
+    assert ratio <= 1
 
 
 @pytest.mark.parametrize("shape", [(37, 4096), (2, 3, 8192), (5, 1000)])
@@ -147,7 +159,8 @@ def test_add_rms_norm_matches_reference(xdt, ydt, shape, with_gs):
     torch.testing.assert_close(y.float().cpu(), yr.detach(), **tol)
     torch.testing.assert_close(xg.grad.float().cpu(), xr.grad, **tol)
     torch.testing.assert_close(dg.grad.float().cpu(), dr.grad, **tol)
-    torch.testing.assert_close(wg.grad.cpu(), wr.grad, rtol=3e-2 if lo else 1e-3, atol=3e-1 if lo else 1e-3)
+    # the backward reads the s the forward stored (rounded to xdt) with the unrounded sum's statistics
+    _assert_dw(wg.grad, s.detach(), w, gy, stats_from=x.double() + d.double())
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
