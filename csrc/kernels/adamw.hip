@@ -99,10 +99,6 @@ __global__ __launch_bounds__(kT) void adamw_kernel(float* __restrict__ master, f
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-}  // namespace
-
-namespace {
-
 template <bool CLIP>
 int launch_adamw(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16, float lr,
                  float b1, float b2, float eps, float wd, int step, float grad_scale, const float* sumsq,
@@ -142,11 +138,6 @@ int pto_adamw_step_scaled(float* master, float* m, float* v, const void* grad, v
                           void* stream) {
   return launch_adamw<false>(master, m, v, grad, out, n, grad_bf16, lr, b1, b2, eps, wd, step, grad_scale, nullptr,
                              0.f, stream);
-}
-
-int pto_adamw_step(float* master, float* m, float* v, const void* grad, void* out, long n, int grad_bf16,
-                   float lr, float b1, float b2, float eps, float wd, int step, void* stream) {
-  return pto_adamw_step_scaled(master, m, v, grad, out, n, grad_bf16, lr, b1, b2, eps, wd, step, 1.f, stream);
 }
 
 // pto_adamw_step_scaled with the gradient also multiplied by min(1, max_norm / (sqrt(*sumsq) + 1e-6)):

@@ -188,7 +188,6 @@ _SIGNATURES = {
     "pto_xent_fwd": [_VP, _VP, _VP, _VP, _L, _I, _L, _I, _VP],
     "pto_xent_bwd": [_VP, _VP, _VP, _VP, _VP, _L, _I, _L, _I, _VP],
     # adamw.hip
-    "pto_adamw_step": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _VP],
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
     "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
     # gradclip.hip

@@ -4,7 +4,8 @@ The norm pass of ``MasterAdamW(max_grad_norm=...)`` and ``ZeroAdamW(max_grad_nor
 ``pto_grad_sumsq`` launch per buffer, each writing its per-block partials into its own
 consecutive region of one workspace, then one ``pto_grad_sumsq_finish`` launch that leaves
 ``sum(g^2)`` and the norm in two device floats.  ``pto_adamw_step_clipped`` reads the sum on the
-device; nothing here reads it on the host.
+device; nothing here reads it on the host.  ``GlobalGradNorm`` is what the optimizers hold: that
+pass (or, on the CPU, the same sum in PyTorch), the all-reduce across ranks, and the result.
 
 No float atomics: the number of partials and the order of every sum depend on the buffer
 lengths alone, so the norm is bitwise reproducible and the same on every replica.
@@ -15,6 +16,7 @@ import ctypes
 from typing import Dict, List, Sequence, Tuple
 
 import torch
+import torch.distributed as dist
 
 from . import _native
 
@@ -66,3 +68,42 @@ class DeviceGradNorm:
             off += k
         _native.check(lib.pto_grad_sumsq_finish(base, total, self.out.data_ptr(), stream), "grad_sumsq_finish")
         return self.out
+
+
+class GlobalGradNorm:
+    """The ``max_grad_norm`` state of one optimizer (``MasterAdamW``, ``ZeroAdamW``): the norm pass
+    over the step's gradient buffers, its two-float result and, on the CPU, the clip factor.
+    ``group`` / ``world``: each rank passes its own shards and the sum of squares is all-reduced."""
+
+    def __init__(self, max_norm, group=None, world: int = 1):
+        if not max_norm > 0:
+            raise ValueError("max_grad_norm: a positive number, or None for no clipping")
+        self.max_norm, self.group, self.world = float(max_norm), group, world
+        self.out = None      # [sum of squares, norm] of the last run, on the gradients' device
+        self.coef = None     # CPU: clip_coef of the last run (on the GPU, AdamW derives it from out)
+        self._device = None  # DeviceGradNorm, created by the first GPU run
+
+    def run(self, items: Sequence[Tuple[torch.Tensor, float]]) -> torch.Tensor:
+        """Norm of ``scale * g`` over every ``(g, scale)``; on the GPU enqueued on the current
+        stream and never read by the host."""
+        if items[0][0].is_cuda:
+            if self._device is None:
+                self._device = DeviceGradNorm()
+            out = self.out = self._device.run(items)
+            if self.world > 1:
+                dist.all_reduce(out[:1], op=dist.ReduceOp.SUM, group=self.group)
+                torch.sqrt(out[:1], out=out[1:])
+        else:
+            sumsq = torch.zeros(1, dtype=torch.float32)
+            for g, scale in items:
+                sumsq += (g.float() * scale).pow(2).sum()
+            if self.world > 1:
+                dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.group)
+            self.out = torch.cat([sumsq, sumsq.sqrt()])
+            self.coef = clip_coef(self.out[1], self.max_norm)
+        return self.out
+
+    def last_grad_norm(self):
+        """The global norm of the last run, before clipping, as a 0-dim tensor on the gradients'
+        device (``None`` before the first run).  Does not synchronise."""
+        return None if self.out is None else self.out[1]

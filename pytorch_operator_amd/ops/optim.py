@@ -4,11 +4,12 @@
 tensors the bf16 autocast matmuls read directly, so the per-step fp32->bf16 weight casts
 and bf16->fp32 gradient casts disappear -- and ``MasterAdamW`` keeps an fp32 master copy
 of those weights plus fp32 moments.  Other parameters (embedding, RMSNorm weights) stay
-fp32 and are their own master.  One fused HIP pass per parameter updates master, m, v
-and rewrites the bf16 weight.  Update rule = ``torch.optim.AdamW`` (decoupled decay,
-bias-corrected moments), applied to the fp32 master.
+fp32 and are their own master.  One fused HIP pass per parameter (``adamw_launch``) updates
+master, m, v and rewrites the bf16 weight.  Update rule = ``torch.optim.AdamW`` (decoupled
+decay, bias-corrected moments), applied to the fp32 master.
 
-On CPU the same update runs in PyTorch (CPU tests, gloo plumbing).
+On CPU the same update runs in PyTorch (``MasterAdamW._step_reference``: CPU tests, gloo
+plumbing).  ``parallel/zero.py`` applies both to its bucket shards.
 """
 from __future__ import annotations
 
@@ -56,17 +57,17 @@ class MasterAdamW(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.overlap = overlap
         self._side = None
-        if max_grad_norm is not None and not max_grad_norm > 0:
-            raise ValueError("max_grad_norm: a positive number, or None for no clipping")
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self._norm = None      # DeviceGradNorm (GPU), created by the first clipped step
-        self._norm_out = None  # [sum of squares, norm] of the last clipped step
+        self._clip = None  # gradclip.GlobalGradNorm: norm pass + result of the last clipped step
+        if max_grad_norm is not None:
+            from .gradclip import GlobalGradNorm
+            self._clip = GlobalGradNorm(max_grad_norm)
+        self.max_grad_norm = self._clip and self._clip.max_norm
 
     def last_grad_norm(self):
         """Global gradient norm of the last ``step()`` before clipping, as a 0-dim tensor on the
         parameters' device (``None`` without ``max_grad_norm`` or before the first step).  Does not
         synchronise: with ``overlap=True`` the value is written on the side stream."""
-        return None if self._norm_out is None else self._norm_out[1]
+        return None if self._clip is None else self._clip.last_grad_norm()
 
     def _state(self, p):
         st = self.state[p]
@@ -109,37 +110,10 @@ class MasterAdamW(torch.optim.Optimizer):
         return loss
 
     def _step_all(self, side):
-        if self.max_grad_norm is not None:
-            return self._step_all_clipped(side)
-        for group in self.param_groups:
-            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.dtype not in (torch.float32, torch.bfloat16):
-                    raise TypeError(f"MasterAdamW: fp32/bf16 parameters only, got {p.dtype}")
-                st = self._state(p)
-                st["step"] += 1
-                master = st["master"] if st["master"] is not None else p
-                # the DDP fp32 comm hook's reduced gradient (harness/ddp_train.py), else .grad
-                g32 = getattr(p, "_pto_grad32", None)
-                if g32 is not None:
-                    del p._pto_grad32
-                g = g32 if g32 is not None else p.grad
-                if p.is_cuda:
-                    if side is not None:
-                        g.record_stream(side)  # the next backward may reuse the memory otherwise
-                    self._step_hip(p, g, master, st, lr, b1, b2, eps, wd)
-                    if side is not None:
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                        p._pto_ready = ev
-                else:
-                    self._step_reference(p, g, master, st, lr, b1, b2, eps, wd)
-
-    def _step_all_clipped(self, side):
-        """Two passes over the gradients this step consumes: their global norm, then AdamW with
-        the clip factor (on the GPU both on the current stream -- the side stream under overlap)."""
+        """The gradients this step consumes, in parameter order; with ``max_grad_norm`` their global
+        norm; then AdamW per parameter (on the GPU all on the current stream -- the side stream
+        under overlap)."""
+        clip = self._clip
         work = []
         for group in self.param_groups:
             for p in group["params"]:
@@ -147,46 +121,39 @@ class MasterAdamW(torch.optim.Optimizer):
                     continue
                 if p.dtype not in (torch.float32, torch.bfloat16):
                     raise TypeError(f"MasterAdamW: fp32/bf16 parameters only, got {p.dtype}")
-                g32 = getattr(p, "_pto_grad32", None)
-                if g32 is not None:
+                # the DDP fp32 comm hook's reduced gradient (harness/ddp_train.py), else .grad
+                g = getattr(p, "_pto_grad32", None)
+                if g is not None:
                     del p._pto_grad32
-                g = g32 if g32 is not None else p.grad
+                else:
+                    g = p.grad
                 if p.is_cuda:
                     if side is not None:
-                        g.record_stream(side)
-                    g = self._hip_grad(p, g)  # fixed up once, read by both passes
+                        g.record_stream(side)  # the next backward may reuse the memory otherwise
+                    if clip is not None:
+                        g = self._hip_grad(p, g)  # fixed up once, read by both passes
                 work.append((group, p, g))
-        if not work:
-            return
-        if len({p.is_cuda for _, p, _ in work}) > 1:
-            raise ValueError("MasterAdamW(max_grad_norm): parameters on the GPU and on the CPU in one optimizer")
-        cuda = work[0][1].is_cuda
-        if cuda:
-            from .gradclip import DeviceGradNorm
-            if self._norm is None:
-                self._norm = DeviceGradNorm()
-            self._norm_out = self._norm.run([(g, 1.0) for _, _, g in work if g.numel()])
-            coef = None
-        else:
-            from .gradclip import clip_coef
-            sumsq = torch.zeros((), dtype=torch.float32)
-            for _, _, g in work:
-                sumsq += g.float().pow(2).sum()
-            self._norm_out = torch.stack([sumsq, sumsq.sqrt()])
-            coef = clip_coef(self._norm_out[1], self.max_grad_norm)
+        if clip is not None and work:
+            if len({p.is_cuda for _, p, _ in work}) > 1:
+                raise ValueError("MasterAdamW(max_grad_norm): parameters on the GPU and on the CPU in one optimizer")
+            clip.run([(g, 1.0) for _, _, g in work if g.numel()])
         for group, p, g in work:
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             st = self._state(p)
             st["step"] += 1
             master = st["master"] if st["master"] is not None else p
-            if cuda:
-                self._launch_hip(p, g, master, st, lr, b1, b2, eps, wd, clip=(self._norm_out, self.max_grad_norm))
+            if p.is_cuda:
+                if clip is None:
+                    g = self._hip_grad(p, g)  # a fix-up copy lives until this launch only
+                adamw_launch(master, st["exp_avg"], st["exp_avg_sq"], g, p if master is not p else None, p.numel(),
+                             st["step"], lr, b1, b2, eps, wd,
+                             clip=None if clip is None else (clip.out, clip.max_norm))
                 if side is not None:
                     ev = torch.cuda.Event()
                     ev.record(side)
                     p._pto_ready = ev
             else:
-                self._step_reference(p, g.float() * coef, master, st, lr, b1, b2, eps, wd)
+                self._step_reference(p, g if clip is None else g.float() * clip.coef, master, st, lr, b1, b2, eps, wd)
 
     @staticmethod
     def _step_reference(p, g, master, st, lr, b1, b2, eps, wd):
@@ -209,26 +176,22 @@ class MasterAdamW(torch.optim.Optimizer):
             raise TypeError("MasterAdamW: contiguous fp32/bf16 parameters and gradients only")
         return g
 
-    @classmethod
-    def _step_hip(cls, p, g, master, st, lr, b1, b2, eps, wd):
-        cls._launch_hip(p, cls._hip_grad(p, g), master, st, lr, b1, b2, eps, wd)
 
-    @staticmethod
-    def _launch_hip(p, g, master, st, lr, b1, b2, eps, wd, clip=None):
-        out = p.data_ptr() if master is not p else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-        lib = _native.load()
-        if clip is None:
-            _native.check(lib.pto_adamw_step(
-                master.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), g.data_ptr(), out,
-                p.numel(), 1 if g.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd, st["step"], stream),
-                "adamw_step")
-        else:
-            sumsq, max_norm = clip  # the device scalar of gradclip.hip's finish kernel
-            _native.check(lib.pto_adamw_step_clipped(
-                master.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), g.data_ptr(), out,
-                p.numel(), 1 if g.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd, st["step"], 1.0,
-                sumsq.data_ptr(), max_norm, stream), "adamw_step_clipped")
+def adamw_launch(master, exp_avg, exp_avg_sq, grad, out, n, step, lr, b1, b2, eps, wd, grad_scale=1.0, clip=None):
+    """One fused AdamW pass (``csrc/kernels/adamw.hip``) over ``n`` elements on the current stream:
+    the package's only call of the ``pto_adamw_*`` entry points.  ``out``: the bf16 weight to
+    refresh (``None``: ``master`` is the parameter).  ``grad_scale`` multiplies the gradient first.
+    ``clip=(norm_out, max_norm)``: also clip by the global norm whose sum of squares is the device
+    float ``norm_out[0]`` (``gradclip.GlobalGradNorm``)."""
+    lib = _native.load()
+    args = (master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr(),
+            None if out is None else out.data_ptr(), n, 1 if grad.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd,
+            step, grad_scale)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(master.device).cuda_stream)
+    if clip is None:
+        _native.check(lib.pto_adamw_step_scaled(*args, stream), "adamw_step")
+    else:
+        _native.check(lib.pto_adamw_step_clipped(*args, clip[0].data_ptr(), clip[1], stream), "adamw_step_clipped")
 
 
 def install_overlap(model: nn.Module) -> int:

@@ -36,12 +36,13 @@ digest of both paths equal on gloo).
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
+
+from ..ops.optim import MasterAdamW, adamw_launch
 
 _ALIGN = 64  # shard lengths are multiples of this (16-byte aligned fp32 / bf16 shard pointers)
 
@@ -152,15 +153,14 @@ class ZeroAdamW:
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  group=None, bucket_mb: float = 256.0, reduce_dtype=torch.float32, grad_view: bool = True,
                  max_grad_norm=None):
-        if max_grad_norm is not None and not max_grad_norm > 0:
-            raise ValueError("max_grad_norm: a positive number, or None for no clipping")
-        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        self._norm = None      # ops.gradclip.DeviceGradNorm (GPU), created by the first clipped step
-        self._norm_out = None  # [sum of squares, norm] of the last clipped step
-        self._coef = None      # CPU path: the clip factor of the current step
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self._clip = None  # ops.gradclip.GlobalGradNorm: norm pass + result of the last clipped step
+        if max_grad_norm is not None:
+            from ..ops.gradclip import GlobalGradNorm
+            self._clip = GlobalGradNorm(max_grad_norm, group, self.world)
+        self.max_grad_norm = self._clip and self._clip.max_norm
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.t = 0
         # per-parameter AdamW step counts (bias correction), as MasterAdamW's st["step"]: at world 1
@@ -300,15 +300,13 @@ class ZeroAdamW:
                         self._deposit(b.grad32[off:off + p.numel()], p.grad.reshape(-1), b.unscaled)
                         p.grad = None
                 self._reduce_scatter(b)
-        if self.max_grad_norm is not None:
-            self._grad_norm_pass()
+        if self._clip is not None:
+            # pass 1 of a clipped step: global norm of the averaged gradient, left on the device
+            self._clip.run([(self._reduced(b), 1.0 / self.world if b.unscaled else 1.0)
+                            for b in reversed(self.buckets)])
         # forward order (the last bucket holds the first layers): their all-gathers go first
         for b in reversed(self.buckets):
-            if b.rs_work is not None:
-                b.rs_work.wait()
-                b.rs_work = None
-            if self.world > 1:
-                b.release_grad()  # the shard holds what AdamW needs (stream-ordered after the wait)
+            self._reduced(b)
             # parameters grouped by their step count after this step (world > 1: every parameter
             # steps -- a missing gradient is a zero contribution, DDP's semantics); each group is
             # one AdamW pass over the bucket with the other ranges saved and restored around it
@@ -336,39 +334,22 @@ class ZeroAdamW:
             b.arrived.clear()
         return loss
 
-    def _grad_norm_pass(self) -> None:
-        """Pass 1 of a clipped step: global norm of the averaged gradient, left on the device."""
-        items = []
-        for b in reversed(self.buckets):
-            if b.rs_work is not None:
-                b.rs_work.wait()
-                b.rs_work = None
-            if self.world > 1:
-                b.release_grad()
-            items.append((b.gshard, 1.0 / self.world if b.unscaled else 1.0))
-        if items[0][0].is_cuda:
-            from ..ops.gradclip import DeviceGradNorm
-            if self._norm is None:
-                self._norm = DeviceGradNorm()
-            out = self._norm_out = self._norm.run(items)
-            if self.world > 1:
-                dist.all_reduce(out[:1], op=dist.ReduceOp.SUM, group=self.group)
-                torch.sqrt(out[:1], out=out[1:])
-        else:
-            from ..ops.gradclip import clip_coef
-            sumsq = torch.zeros(1, dtype=torch.float32)
-            for g, scale in items:
-                sumsq += (g.float() * scale).pow(2).sum()
-            if self.world > 1:
-                dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.group)
-            self._norm_out = torch.cat([sumsq, sumsq.sqrt()])
-            self._coef = clip_coef(self._norm_out[1], self.max_grad_norm)
+    def _reduced(self, b: _Bucket) -> torch.Tensor:
+        """The bucket's gradient shard, its reduce-scatter waited for.  At world > 1 the full
+        gradient bucket is released: the shard holds what the norm pass and AdamW need
+        (stream-ordered after the wait)."""
+        if b.rs_work is not None:
+            b.rs_work.wait()
+            b.rs_work = None
+        if self.world > 1:
+            b.release_grad()
+        return b.gshard
 
     def last_grad_norm(self):
         """Global norm of the averaged gradient at the last ``step()``, before clipping, as a 0-dim
         tensor on the parameters' device (``None`` without ``max_grad_norm`` or before the first
         step).  Does not synchronise."""
-        return None if self._norm_out is None else self._norm_out[1]
+        return None if self._clip is None else self._clip.last_grad_norm()
 
     @staticmethod
     def _save_ranges(b: _Bucket, ranges) -> list:
@@ -394,25 +375,14 @@ class ZeroAdamW:
         b1, b2 = self.betas
         w = b.w_shard()
         master = b.master if b.master is not None else w
+        clip = self._clip
         if w.is_cuda:
-            from ..ops import _native
-            stream = ctypes.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
-            out = w.data_ptr() if b.master is not None else None
-            if self.max_grad_norm is not None:
-                _native.check(_native.load().pto_adamw_step_clipped(
-                    master.data_ptr(), b.exp_avg.data_ptr(), b.exp_avg_sq.data_ptr(), b.gshard.data_ptr(), out,
-                    b.shard, 1 if b.gshard.dtype == torch.bfloat16 else 0, self.lr, b1, b2, self.eps,
-                    self.weight_decay, t, 1.0 / self.world if b.unscaled else 1.0, self._norm_out.data_ptr(),
-                    self.max_grad_norm, stream), "adamw_step_clipped")
-                return
-            _native.check(_native.load().pto_adamw_step_scaled(
-                master.data_ptr(), b.exp_avg.data_ptr(), b.exp_avg_sq.data_ptr(), b.gshard.data_ptr(), out,
-                b.shard, 1 if b.gshard.dtype == torch.bfloat16 else 0, self.lr, b1, b2, self.eps,
-                self.weight_decay, t, 1.0 / self.world if b.unscaled else 1.0, stream), "adamw_step")
+            adamw_launch(master, b.exp_avg, b.exp_avg_sq, b.gshard, w if b.master is not None else None, b.shard, t,
+                         self.lr, b1, b2, self.eps, self.weight_decay, 1.0 / self.world if b.unscaled else 1.0,
+                         None if clip is None else (clip.out, clip.max_norm))
         else:
-            from ..ops.optim import MasterAdamW
             st = {"step": t, "exp_avg": b.exp_avg, "exp_avg_sq": b.exp_avg_sq}
-            g = b.gshard if self.max_grad_norm is None else b.gshard.float() * self._coef
+            g = b.gshard if clip is None else b.gshard.float() * clip.coef
             MasterAdamW._step_reference(w, g, master, st, self.lr, b1, b2, self.eps, self.weight_decay)
 
     def _wait_weights(self, buckets) -> None:

@@ -33,7 +33,7 @@ for step in range(11):
     loss.backward()
     opt.step()
     torch.cuda.synchronize()
-    o = opt._norm_out.cpu()
+    o = opt._clip.out.cpu()
     rows.append({"step": step + 1, "loss": float(loss.detach()), "sumsq": float(o[0]), "sumsq_bits": int(o[:1].view(torch.int32)),
                  "grad_norm": float(o[1])})
     print(json.dumps(rows[-1]), flush=True)
