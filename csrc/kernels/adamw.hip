@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pto_vec.h"
+
 namespace {
 
 constexpr int kT = 256;
@@ -22,14 +24,6 @@ constexpr int kT = 256;
 struct AdamArgs {
   float lr, b1, b2, eps, wd, inv_bc1, inv_sqrt_bc2, gscale;
 };
-
-// Round to nearest even.  A NaN stays a NaN (quiet, same sign): the rounding carry would run out
-// of an all-ones mantissa into the exponent and sign (0xffffffff -> +0.0, 0x7fffffff -> -0.0).
-__device__ __forceinline__ uint32_t bf16_rne(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // The fused multiply-adds are spelled out and the compiler's own contraction is off: left to
 // choose, it fused different products in different instantiations (and in different lanes of one
@@ -66,16 +60,8 @@ __global__ __launch_bounds__(kT) void adamw_kernel(float* __restrict__ master, f
       float4 m = reinterpret_cast<float4*>(mom)[i];
       float4 v = reinterpret_cast<float4*>(var)[i];
       float g[4];
-      if (GBF16) {
-        const uint2 q = reinterpret_cast<const uint2*>(grad)[i];
-        g[0] = __uint_as_float(q.x << 16);
-        g[1] = __uint_as_float(q.x & 0xffff0000u);
-        g[2] = __uint_as_float(q.y << 16);
-        g[3] = __uint_as_float(q.y & 0xffff0000u);
-      } else {
-        const float4 q = reinterpret_cast<const float4*>(grad)[i];
-        g[0] = q.x; g[1] = q.y; g[2] = q.z; g[3] = q.w;
-      }
+      if (GBF16) pto::vload(reinterpret_cast<const uint16_t*>(grad) + 4 * i, g);
+      else pto::vload(reinterpret_cast<const float*>(grad) + 4 * i, g);
       adam1(p.x, m.x, v.x, g[0], a);
       adam1(p.y, m.y, v.y, g[1], a);
       adam1(p.z, m.z, v.z, g[2], a);
@@ -84,14 +70,13 @@ __global__ __launch_bounds__(kT) void adamw_kernel(float* __restrict__ master, f
       reinterpret_cast<float4*>(mom)[i] = m;
       reinterpret_cast<float4*>(var)[i] = v;
       if (OUTBF16)
-        reinterpret_cast<uint2*>(out)[i] =
-            make_uint2(bf16_rne(p.x) | (bf16_rne(p.y) << 16), bf16_rne(p.z) | (bf16_rne(p.w) << 16));
+        reinterpret_cast<uint2*>(out)[i] = make_uint2(pto::bf16_pack(p.x, p.y), pto::bf16_pack(p.z, p.w));
     } else {
       for (long j = n4 * 4; j < n; ++j) {
-        const float g = GBF16 ? __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(grad)[j] << 16)
-                              : reinterpret_cast<const float*>(grad)[j];
+        const float g = GBF16 ? pto::load1(reinterpret_cast<const uint16_t*>(grad) + j)
+                              : pto::load1(reinterpret_cast<const float*>(grad) + j);
         const float p = adam1(master[j], mom[j], var[j], g, a);
-        if (OUTBF16) out[j] = (uint16_t)bf16_rne(p);
+        if (OUTBF16) pto::store1(out + j, p);
       }
     }
   }

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pto_common.h"
+#include "pto_vec.h"
 
 namespace {
 
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(kT) void grad_sumsq_kernel(const void* __restrict__
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         if (BF16) {
-          acc[k] = sq_acc(__uint_as_float(q[k][c] << 16), scale, acc[k]);
-          acc[k] = sq_acc(__uint_as_float(q[k][c] & 0xffff0000u), scale, acc[k]);
+          acc[k] = sq_acc(pto::bf_lo(q[k][c]), scale, acc[k]);
+          acc[k] = sq_acc(pto::bf_hi(q[k][c]), scale, acc[k]);
         } else {
           acc[k] = sq_acc(__uint_as_float(q[k][c]), scale, acc[k]);
         }
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kT) void grad_sumsq_kernel(const void* __restrict__
   // scalar tail (< one vector): one element per lane of block 0
   const long t = nv * kE + threadIdx.x;
   if (blockIdx.x == 0 && t < n) {
-    const float x = BF16 ? __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(grad)[t] << 16)
+    const float x = BF16 ? pto::bf2f(reinterpret_cast<const uint16_t*>(grad)[t])
                          : reinterpret_cast<const float*>(grad)[t];
     acc[0] = sq_acc(x, scale, acc[0]);
   }

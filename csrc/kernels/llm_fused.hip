@@ -25,62 +25,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pto_vec.h"
+
 namespace {
 
 constexpr int kT = 256;
 
-struct V8 {
-  float v[8];
-};
-
-__device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-// Round to nearest even.  A NaN stays a NaN (quiet, same sign): the rounding carry would run out
-// of an all-ones mantissa into the exponent and sign (0xffffffff -> +0.0, 0x7fffffff -> -0.0).
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-template <typename T>
-struct Vec;
-
-template <>
-struct Vec<float> {
-  static __device__ __forceinline__ V8 load(const float* p) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    return V8{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-  }
-  static __device__ __forceinline__ void store(float* p, const V8& r) {
-    reinterpret_cast<float4*>(p)[0] = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    reinterpret_cast<float4*>(p)[1] = make_float4(r.v[4], r.v[5], r.v[6], r.v[7]);
-  }
-  static __device__ __forceinline__ float load1(const float* p) { return *p; }
-  static __device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-};
-
-template <>
-struct Vec<uint16_t> {  // bf16 bits
-  static __device__ __forceinline__ V8 load(const uint16_t* p) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-    V8 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      r.v[2 * i] = __uint_as_float(w[i] << 16);
-      r.v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-    return r;
-  }
-  static __device__ __forceinline__ void store(uint16_t* p, const V8& r) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = (uint32_t)f2bf(r.v[2 * i]) | ((uint32_t)f2bf(r.v[2 * i + 1]) << 16);
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  static __device__ __forceinline__ float load1(const uint16_t* p) { return bf2f(*p); }
-  static __device__ __forceinline__ void store1(uint16_t* p, float v) { *p = f2bf(v); }
-};
+using V8 = pto::Vec<8>;
+using pto::vload;
+using pto::vstore;
 
 // ---------------------------------------------------------------------------------- rope
 template <typename T>
@@ -92,7 +45,7 @@ __global__ __launch_bounds__(kT) void rope_kernel(const T* __restrict__ x, const
     const long row = g / gpr;
     const int c8 = (int)(g - row * gpr) * 8;
     const int s = (int)((row / H) % S);
-    const V8 in = Vec<T>::load(x + row * D + c8);
+    const V8 in = vload<8>(x + row * D + c8);
     const float4 cv = *reinterpret_cast<const float4*>(cosb + (long)s * (D / 2) + c8 / 2);
     const float4 sv = *reinterpret_cast<const float4*>(sinb + (long)s * (D / 2) + c8 / 2);
     const float cs[4] = {cv.x, cv.y, cv.z, cv.w}, sn[4] = {sign * sv.x, sign * sv.y, sign * sv.z, sign * sv.w};
@@ -103,7 +56,7 @@ __global__ __launch_bounds__(kT) void rope_kernel(const T* __restrict__ x, const
       out.v[2 * i] = x0 * cs[i] - x1 * sn[i];
       out.v[2 * i + 1] = x0 * sn[i] + x1 * cs[i];
     }
-    Vec<T>::store(y + row * D + c8, out);
+    vstore(y + row * D + c8, out);
   }
 }
 
@@ -131,7 +84,7 @@ __global__ __launch_bounds__(kT) void rope_qkv_kernel(T* __restrict__ pk, T* __r
       rot = false;
     }
     T* packed = pk + tok * W + c;
-    const V8 in = dir == 0 ? Vec<T>::load(packed) : Vec<T>::load(other);
+    const V8 in = dir == 0 ? vload<8>(packed) : vload<8>(other);
     V8 out = in;
     if (rot) {
       const int s = (int)(tok % S);
@@ -146,12 +99,18 @@ __global__ __launch_bounds__(kT) void rope_qkv_kernel(T* __restrict__ pk, T* __r
         out.v[2 * i + 1] = x0 * sn[i] + x1 * cs[i];
       }
     }
-    Vec<T>::store(dir == 0 ? other : packed, out);
+    vstore(dir == 0 ? other : packed, out);
   }
 }
 
 // -------------------------------------------------------------------------------- swiglu
 __device__ __forceinline__ float sigmoid(float a) { return 1.f / (1.f + __expf(-a)); }
+__device__ __forceinline__ float swiglu_y(float a, float b) { return a * sigmoid(a) * b; }
+__device__ __forceinline__ void swiglu_grad(float g, float a, float b, float& da, float& db) {
+  const float sg = sigmoid(a);
+  da = g * b * sg * (1.f + a * (1.f - sg));
+  db = g * (a * sg);  // silu first: dy * a can overflow where silu(a) is -0
+}
 
 // Packed form: x [rows, 2F] (a = x[:, :F], b = x[:, F:]), y / dy [rows, F].  F % 8 == 0.
 template <typename T>
@@ -162,11 +121,11 @@ __global__ __launch_bounds__(kT) void swiglu_packed_fwd_kernel(const T* __restri
   for (long g = (long)blockIdx.x * kT + threadIdx.x; g < groups; g += (long)gridDim.x * kT) {
     const long r = g / gpr;
     const int c = (int)(g - r * gpr) * 8;
-    const V8 av = Vec<T>::load(x + r * 2 * F + c), bv = Vec<T>::load(x + r * 2 * F + F + c);
+    const V8 av = vload<8>(x + r * 2 * F + c), bv = vload<8>(x + r * 2 * F + F + c);
     V8 o;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = av.v[i] * sigmoid(av.v[i]) * bv.v[i];
-    Vec<T>::store(y + r * F + c, o);
+    for (int i = 0; i < 8; ++i) o.v[i] = swiglu_y(av.v[i], bv.v[i]);
+    vstore(y + r * F + c, o);
   }
 }
 
@@ -178,17 +137,13 @@ __global__ __launch_bounds__(kT) void swiglu_packed_bwd_kernel(const T* __restri
   for (long g = (long)blockIdx.x * kT + threadIdx.x; g < groups; g += (long)gridDim.x * kT) {
     const long r = g / gpr;
     const int c = (int)(g - r * gpr) * 8;
-    const V8 gv = Vec<T>::load(dy + r * F + c);
-    const V8 av = Vec<T>::load(x + r * 2 * F + c), bv = Vec<T>::load(x + r * 2 * F + F + c);
+    const V8 gv = vload<8>(dy + r * F + c);
+    const V8 av = vload<8>(x + r * 2 * F + c), bv = vload<8>(x + r * 2 * F + F + c);
     V8 oa, ob;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float sg = sigmoid(av.v[i]);
-      oa.v[i] = gv.v[i] * bv.v[i] * sg * (1.f + av.v[i] * (1.f - sg));
-      ob.v[i] = gv.v[i] * (av.v[i] * sg);  // silu first: dy * a can overflow where silu(a) is -0
-    }
-    Vec<T>::store(dx + r * 2 * F + c, oa);
-    Vec<T>::store(dx + r * 2 * F + F + c, ob);
+    for (int i = 0; i < 8; ++i) swiglu_grad(gv.v[i], av.v[i], bv.v[i], oa.v[i], ob.v[i]);
+    vstore(dx + r * 2 * F + c, oa);
+    vstore(dx + r * 2 * F + F + c, ob);
   }
 }
 
@@ -198,15 +153,14 @@ __global__ __launch_bounds__(kT) void swiglu_fwd_kernel(const T* __restrict__ a,
   const long n8 = n / 8;
   for (long g = (long)blockIdx.x * kT + threadIdx.x; g <= n8; g += (long)gridDim.x * kT) {
     if (g < n8) {
-      const V8 av = Vec<T>::load(a + g * 8), bv = Vec<T>::load(b + g * 8);
+      const V8 av = vload<8>(a + g * 8), bv = vload<8>(b + g * 8);
       V8 o;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o.v[i] = av.v[i] * sigmoid(av.v[i]) * bv.v[i];
-      Vec<T>::store(y + g * 8, o);
+      for (int i = 0; i < 8; ++i) o.v[i] = swiglu_y(av.v[i], bv.v[i]);
+      vstore(y + g * 8, o);
     } else {
       for (long i = n8 * 8; i < n; ++i) {
-        const float av = Vec<T>::load1(a + i);
-        Vec<T>::store1(y + i, av * sigmoid(av) * Vec<T>::load1(b + i));
+        pto::store1(y + i, swiglu_y(pto::load1(a + i), pto::load1(b + i)));
       }
     }
   }
@@ -219,22 +173,19 @@ __global__ __launch_bounds__(kT) void swiglu_bwd_kernel(const T* __restrict__ dy
   const long n8 = n / 8;
   for (long g = (long)blockIdx.x * kT + threadIdx.x; g <= n8; g += (long)gridDim.x * kT) {
     if (g < n8) {
-      const V8 gv = Vec<T>::load(dy + g * 8), av = Vec<T>::load(a + g * 8), bv = Vec<T>::load(b + g * 8);
+      const V8 gv = vload<8>(dy + g * 8), av = vload<8>(a + g * 8), bv = vload<8>(b + g * 8);
       V8 oa, ob;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float sg = sigmoid(av.v[i]);
-        oa.v[i] = gv.v[i] * bv.v[i] * sg * (1.f + av.v[i] * (1.f - sg));
-        ob.v[i] = gv.v[i] * (av.v[i] * sg);  // silu first: dy * a can overflow where silu(a) is -0
-      }
-      Vec<T>::store(da + g * 8, oa);
-      Vec<T>::store(db + g * 8, ob);
+      for (int i = 0; i < 8; ++i) swiglu_grad(gv.v[i], av.v[i], bv.v[i], oa.v[i], ob.v[i]);
+      vstore(da + g * 8, oa);
+      vstore(db + g * 8, ob);
     } else {
       for (long i = n8 * 8; i < n; ++i) {
-        const float gv = Vec<T>::load1(dy + i), av = Vec<T>::load1(a + i), bv = Vec<T>::load1(b + i);
-        const float sg = sigmoid(av);
-        Vec<T>::store1(da + i, gv * bv * sg * (1.f + av * (1.f - sg)));
-        Vec<T>::store1(db + i, gv * (av * sg));
+        const float gv = pto::load1(dy + i), av = pto::load1(a + i), bv = pto::load1(b + i);
+        float oa, ob;
+        swiglu_grad(gv, av, bv, oa, ob);
+        pto::store1(da + i, oa);
+        pto::store1(db + i, ob);
       }
     }
   }
@@ -256,7 +207,7 @@ __global__ __launch_bounds__(kX) void xent_fwd_kernel(const T* __restrict__ x, c
   float m = -INFINITY, s = 0.f;
   const int n8 = V / 8;
   for (int g = tid; g < n8; g += kX) {
-    const V8 v = Vec<T>::load(xr + (long)g * 8);
+    const V8 v = vload<8>(xr + (long)g * 8);
     float mx = v.v[0];
 #pragma unroll
     for (int i = 1; i < 8; ++i) mx = fmaxf(mx, v.v[i]);
@@ -289,7 +240,7 @@ __global__ __launch_bounds__(kX) void xent_fwd_kernel(const T* __restrict__ x, c
     const float lse = M + __logf(Ssum);
     const long t = tgt[row];
     lse_out[row] = lse;
-    loss_out[row] = (t == ignore_index || t < 0 || t >= V) ? 0.f : lse - Vec<T>::load1(xr + t);
+    loss_out[row] = (t == ignore_index || t < 0 || t >= V) ? 0.f : lse - pto::load1(xr + t);
   }
 }
 
@@ -308,13 +259,13 @@ __global__ __launch_bounds__(kX) void xent_bwd_kernel(const T* x, const long* __
   const float lse = lse_in[row], sc = ign ? 0.f : scale[0];
   const int n8 = V / 8;
   for (int g = threadIdx.x; g < n8; g += kX) {
-    V8 v = Vec<T>::load(xr + (long)g * 8);
+    V8 v = vload<8>(xr + (long)g * 8);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float p = __expf(v.v[i] - lse);
       v.v[i] = (p - ((long)(g * 8 + i) == t ? 1.f : 0.f)) * sc;
     }
-    Vec<T>::store(dr + (long)g * 8, v);
+    vstore(dr + (long)g * 8, v);
   }
 }
 

@@ -2,13 +2,14 @@
 (cross-entropy, SwiGLU) and adamw.hip -- against fp64 arithmetic on the same values.
 
 tests/test_llm_gpu.py checks these kernels at a few friendly shapes; this module walks the
-branches those shapes never take: the scalar RMSNorm kernels (odd D, unaligned views) and every
-PER / P4 instantiation, cross-entropy at the sizes that change its loop trip count, with boundary
-targets and -inf (masked-vocabulary) logits, SwiGLU tails, saturating inputs and the second
-grid-stride trip, all eight AdamW instantiations through the C entry points with tail-only and
-grid-stride sizes, and the NaN rule of the bf16 rounding.  Inputs are drawn on the CPU with a
-seeded generator and rounded to the kernel's input dtype first, so both sides start from the
-same values; the references and the derived bounds are in tests/llm_refs.py.
+branches those shapes never take: RMSNorm at one element per access (W = 1: odd D, unaligned
+views) and every W / P instantiation, cross-entropy at the sizes that change its loop trip
+count, with boundary targets and -inf (masked-vocabulary) logits, SwiGLU tails, saturating
+inputs and the second grid-stride trip, all eight AdamW instantiations through the C entry
+points with tail-only and grid-stride sizes, and the NaN rule of the bf16 rounding.  Inputs are
+drawn on the CPU with a seeded generator and rounded to the kernel's input dtype first, so both
+sides start from the same values; the references and the derived bounds are in
+tests/llm_refs.py.
 """
 import ctypes
 import functools
@@ -55,8 +56,8 @@ def _unaligned(t):
 # ------------------------------------------------------------------------------- RMSNorm
 PAIRS = [(F32, F32), (BF16, BF16), (F32, BF16)]
 PAIR_IDS = ["x32-y32", "xbf16-ybf16", "x32-ybf16"]
-SCALAR_D = [3, 259, 515, 1027, 2051, 4099, 8191]  # PER = 1, 2, 4, 8, 16, 32 (twice)
-VECTOR_D = [4, 1028, 2052, 4100]                   # P4 = 1, 2, 4 and a mostly-empty 8
+SCALAR_D = [3, 259, 515, 1027, 2051, 4099, 8191]  # W = 1: P = 1, 2, 4, 8, 16, 32 (twice)
+VECTOR_D = [4, 1028, 2052, 4100]                   # W = 4: P = 1, 2, 4 and a mostly-empty 8
 ROWS = [1, 9, 17]                                  # _ROWS_PER_BLOCK = 8: 1 row; 8 + 1; 8 + 8 + 1
 
 
@@ -95,8 +96,8 @@ def _rmsnorm_check(label, x, w, dy, xdt, ydt, xg=None, dyg=None):
 @pytest.mark.parametrize("D", SCALAR_D + VECTOR_D)
 @pytest.mark.parametrize("xdt,ydt", PAIRS, ids=PAIR_IDS)
 def test_rmsnorm_every_instantiation_matches_fp64(xdt, ydt, D, rows):
-    """Odd D takes rmsnorm_fwd_kernel / rmsnorm_bwd_kernel (one D per PER instantiation) and the
-    scalar branch of colsum_kernel; D % 4 == 0 takes the vector kernels at P4 = 1, 2, 4, 8."""
+    """Odd D takes rmsnorm_fwd_kernel / rmsnorm_bwd_kernel at W = 1 (one D per P instantiation) and
+    the scalar branch of colsum_kernel; D % 4 == 0 takes them at W = 4, P = 1, 2, 4, 8."""
     x, w, dy = _rmsnorm_inputs(rows, D, xdt, ydt, seed=1000 * D + rows)
     _rmsnorm_check(f"{_NAME[xdt]}->{_NAME[ydt]} D={D} rows={rows}", x, w, dy, xdt, ydt)
 
@@ -106,8 +107,8 @@ def test_rmsnorm_every_instantiation_matches_fp64(xdt, ydt, D, rows):
 @pytest.mark.parametrize("xdt,ydt", PAIRS, ids=PAIR_IDS)
 def test_rmsnorm_unaligned_view_takes_scalar_kernels(xdt, ydt, which, rows):
     """D = 1028 is a multiple of 4, but a contiguous view one element off a 16-byte boundary
-    cannot be read with 16-byte loads: an unaligned x sends forward and backward to the scalar
-    kernels (PER = 8); an unaligned dy alone leaves the forward on the vector path."""
+    cannot be read with 16-byte loads: an unaligned x sends forward and backward to the W = 1
+    kernels (P = 8); an unaligned dy alone leaves the forward at W = 4."""
     D = 1028
     x, w, dy = _rmsnorm_inputs(rows, D, xdt, ydt, seed=77 + rows)
     xg = _unaligned(x) if which == "x" else x.cuda()
@@ -121,8 +122,8 @@ def test_rmsnorm_unaligned_view_takes_scalar_kernels(xdt, ydt, which, rows):
 @pytest.mark.parametrize("D", [1028, 4100, 1027])
 @pytest.mark.parametrize("xdt,ydt", [(F32, BF16), (F32, F32), (BF16, BF16)], ids=["x32-ybf16", "x32-y32", "xbf16-ybf16"])
 def test_add_rms_norm_edge_widths(xdt, ydt, D, with_gs):
-    """Residual-fused RMSNorm at P4 = 2 (D = 1028) and a partly filled P4 = 8 (D = 4100), and at
-    D = 1027, where add_rms_norm falls back to the unfused add + rms_norm (scalar kernels); the
+    """Residual-fused RMSNorm at P = 2 (D = 1028) and a partly filled P = 8 (D = 4100), and at
+    D = 1027, where add_rms_norm falls back to the unfused add + rms_norm (W = 1 kernels); the
     tolerances of test_llm_gpu.test_add_rms_norm_matches_reference, dw at the derived bound."""
     from pytorch_operator_amd.ops.norm import add_rms_norm
     rows = 9
