@@ -26,7 +26,7 @@ import os
 import sys
 import time
 
-MODELS = ("resnet50", "resnet-tiny", "llama3-8b", "llama3-1b", "llama-tiny")
+MODELS = ("resnet50", "resnet-tiny", "llama3-8b", "llama3-1b", "llama-tiny", "llama-mini")
 
 
 def parse_args(argv=None):
@@ -113,12 +113,20 @@ def parse_args(argv=None):
                         "ignored; 0 = off (one document per sequence)")
     p.add_argument("--eos-id", type=int, default=None,
                    help="end-of-text token id for --doc-len-mean (default: the last vocabulary id)")
+    p.add_argument("--grad-accum", type=int, default=1,
+                   help="Llama: micro-batches of --batch-size sequences per optimizer step.  Master-weight / "
+                        "ZeRO: their gradients are summed in fp32 accumulators (csrc/kernels/gradaccum.hip) and "
+                        "reduced once per step; data parallelism needs --zero 1")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
     args = p.parse_args(argv)
     if args.linear_dtype == "fp8" and not (args.model.startswith("llama") and args.dtype == "bf16"):
         p.error("--linear-dtype fp8 is for the Llama models with --dtype bf16")
+    if args.grad_accum < 1:
+        p.error("--grad-accum: a positive number of micro-batches")
+    if args.grad_accum > 1 and not args.model.startswith("llama"):
+        p.error("--grad-accum is for the Llama models")
     return args
 
 
@@ -163,6 +171,7 @@ def build(args, device, world: int = 1):
     with torch.device(device):
         model = Llama(CONFIGS[args.model], checkpoint_layers=args.grad_checkpoint)
     clip = {"max_grad_norm": args.max_grad_norm} if args.max_grad_norm > 0 else {}
+    accum = {"grad_accum": args.grad_accum} if args.grad_accum > 1 else {}
     if use_zero(args, device, world):
         from ..ops.optim import to_bf16_matmul_weights
         from ..parallel.zero import ZeroAdamW
@@ -173,14 +182,14 @@ def build(args, device, world: int = 1):
         opt = ZeroAdamW(model, lr=args.lr or 3e-4, betas=(0.9, 0.95), weight_decay=0.1,
                         bucket_mb=args.zero_bucket_mb,
                         reduce_dtype=torch.bfloat16 if args.allreduce_dtype == "bf16" else torch.float32,
-                        grad_view=bool(args.zero_grad_view), **clip)
+                        grad_view=bool(args.zero_grad_view), **clip, **accum)
         return model, opt
     if use_master_weights(args, device):
         from ..ops.optim import MasterAdamW, install_overlap, to_bf16_matmul_weights
         to_bf16_matmul_weights(model)
         overlap = args.opt_overlap == "on" and device.type == "cuda"
         opt = MasterAdamW(model.parameters(), lr=args.lr or 3e-4, betas=(0.9, 0.95), weight_decay=0.1,
-                          overlap=overlap, **clip)
+                          overlap=overlap, **clip, **accum)
         if overlap:
             install_overlap(model)
         return model, opt
@@ -316,8 +325,15 @@ def main(argv=None) -> int:
     torch.manual_seed(args.seed)
     is_llama = args.model.startswith("llama")
     B = args.batch_size or (1 if is_llama else (256 if use_gpu else 2))
-    model, opt = build(args, dev, world)
+    N = args.grad_accum
     zero = use_zero(args, dev, world)
+    if N > 1 and world > 1 and not zero:
+        # DDP's all-reduce would see only the last micro-batch's gradient
+        print(f"error: --grad-accum {N} on {world} ranks needs the ZeRO-1 optimizer (--zero 1, with master "
+              "weights): the DDP path reduces every backward pass", file=sys.stderr, flush=True)
+        dist.destroy_process_group()
+        return 2
+    model, opt = build(args, dev, world)
     tuning = setup_gemm_tuning(args, dev)
     n_params = sum(p.numel() for p in model.parameters())
     if world > 1 and not zero:
@@ -333,20 +349,29 @@ def main(argv=None) -> int:
     if is_llama:
         from ..models.llama import CONFIGS
         V = CONFIGS[args.model].vocab_size
-        data = torch.randint(0, V, (B, args.seq_len + 1), generator=g).to(dev)
-        doc_start = None
         if args.doc_len_mean > 0:
             from ..ops.attention import doc_starts_from_tokens, validate_doc_start
             eos = V - 1 if args.eos_id is None else args.eos_id
-            # drawn after the tokens from the same generator: the default token stream is unchanged
-            cut = torch.rand(B, args.seq_len + 1, generator=g) < 1.0 / args.doc_len_mean
-            data = torch.where(cut.to(dev), torch.full_like(data, eos), data)
-        x, y = data[:, :-1].contiguous(), data[:, 1:].contiguous()
+
+        def draw():
+            data = torch.randint(0, V, (B, args.seq_len + 1), generator=g).to(dev)
+            doc_start = None
+            if args.doc_len_mean > 0:
+                # drawn after the tokens from the same generator: the default token stream is unchanged
+                cut = torch.rand(B, args.seq_len + 1, generator=g) < 1.0 / args.doc_len_mean
+                data = torch.where(cut.to(dev), torch.full_like(data, eos), data)
+            x, y = data[:, :-1].contiguous(), data[:, 1:].contiguous()
+            if args.doc_len_mean > 0:
+                doc_start = doc_starts_from_tokens(x, eos)
+                validate_doc_start(doc_start)
+                y = y.masked_fill(x == eos, -100)  # that target would be the next document's first token
+            return x, y, doc_start
+
+        x, y, doc_start = draw()
         if args.doc_len_mean > 0:
-            doc_start = doc_starts_from_tokens(x, eos)
-            validate_doc_start(doc_start)
-            y = y.masked_fill(x == eos, -100)  # that target would be the next document's first token
             docs_per_seq = float((x[:, :-1] == eos).sum()) / B + 1.0
+        # --grad-accum: micro-batches 2..N, drawn after everything above (the first is unchanged)
+        micro = [(x, y, doc_start)] + [draw() for _ in range(N - 1)]
     else:
         H = args.image_size if args.model == "resnet50" else 32
         x = torch.randn(B, 3, H, H, generator=g).to(dev)
@@ -369,20 +394,40 @@ def main(argv=None) -> int:
     def grad_norm() -> float:
         return float(torch_norm if torch_clip else opt.last_grad_norm())
 
+    own_accum = hasattr(opt, "accumulate")  # MasterAdamW / ZeroAdamW: fp32 accumulators
+
+    def accum_backward():
+        """N x (forward, backward); returns the mean of the micro-batch losses (on the device)."""
+        total = None
+        for k, (xk, yk, dk) in enumerate(micro):
+            with amp:
+                lk = model(xk, yk) if dk is None else model(xk, yk, doc_start=dk)
+            if own_accum:
+                lk.backward()
+                if k < N - 1:
+                    opt.accumulate()
+            else:
+                (lk / N).backward()  # a plain torch optimizer: .grad accumulates the mean natively
+            total = lk.detach() if total is None else total + lk.detach()
+        return total / N
+
     def step():
         nonlocal gstep, torch_norm
         gstep += 1
         if args.ckpt_dir and args.ckpt_every and gstep % args.ckpt_every == 0:
             pending_ckpt.append(gstep)
         opt.zero_grad(set_to_none=True)
-        with amp:
-            if is_llama and doc_start is not None:
-                loss = model(x, y, doc_start=doc_start)
-            elif is_llama:
-                loss = model(x, y)
-            else:
-                loss = F.cross_entropy(model(x).float(), y)
-        loss.backward()
+        if N > 1:
+            loss = accum_backward()
+        else:
+            with amp:
+                if is_llama and doc_start is not None:
+                    loss = model(x, y, doc_start=doc_start)
+                elif is_llama:
+                    loss = model(x, y)
+                else:
+                    loss = F.cross_entropy(model(x).float(), y)
+            loss.backward()
         if torch_clip:
             torch_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
         opt.step()
@@ -423,7 +468,7 @@ def main(argv=None) -> int:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    samples = args.steps * B * world
+    samples = args.steps * B * world * N
     per_sample = train_flops_per_sample(args)
     unit_tokens = is_llama
     value = samples * (args.seq_len if unit_tokens else 1) / dt
@@ -447,6 +492,8 @@ def main(argv=None) -> int:
                    opt_overlap=args.opt_overlap if res["master_weights"] and not zero else None)
     if args.linear_dtype == "fp8":  # (the default's result line keeps its keys)
         res.update(linear_dtype=args.linear_dtype, grad_format=args.fp8_grad_format)
+    if N > 1:
+        res.update(grad_accum=N)
     if is_llama and doc_start is not None:
         res.update(doc_len_mean=args.doc_len_mean, docs_per_seq=round(docs_per_seq, 2), attn_mask="document")
     if tuning.get("mode") == "tune" and rank == 0:

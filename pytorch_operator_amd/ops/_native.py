@@ -193,8 +193,10 @@ _SIGNATURES = {
     # gradclip.hip
     "pto_grad_sumsq": [_VP, _L, _I, _F, _VP, _L, _VP],
     "pto_grad_sumsq_finish": [_VP, _L, _VP, _VP],
+    # gradaccum.hip
+    "pto_grad_accum": [_VP, _VP, _VP, _L, _I, _I, _VP],
     # fp8_cast.hip
-    "pto_fp8_amax": [_VP, _L, _L, _VP, _L, _VP],
+    "pto_fp8_amax":[_VP, _L, _L, _VP, _L, _VP],
     "pto_fp8_cast": [_VP, _L, _L, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP],
     # batchnorm.hip
     "pto_bn_plan": [_L, _I, ctypes.POINTER(_I)],
@@ -223,7 +225,8 @@ _SIGNATURES = {
     "pto_device_prewarm": [_I, _VP, _VP],
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
-             "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L]}
+             "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
+             "pto_grad_accum_sweep": []}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

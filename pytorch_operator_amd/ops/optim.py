@@ -50,11 +50,26 @@ class MasterAdamW(torch.optim.Optimizer):
     exactly the tensors the step consumes.  On the GPU that is one streaming sum-of-squares pass
     per gradient, one finish launch, and the AdamW launches reading the result on the device
     (``csrc/kernels/gradclip.hip``); the host never sees the norm unless it asks
-    (``last_grad_norm()``)."""
+    (``last_grad_norm()``).
+
+    ``grad_accum=N`` (default 1: off, nothing below exists): N backward passes per step.  Call
+    ``accumulate()`` after each of the first N-1 and ``step()`` after the last.  Every ``.grad`` is
+    folded into an fp32 accumulator of the parameter's shape (``ops/gradaccum.py``: a sequential fp32
+    sum, the first term stored) and freed; the norm pass and AdamW then read the accumulators with
+    1/N as their gradient scale.  The accumulators (4 B per parameter, kept from step to step) are
+    no optimizer state: they are empty at every step boundary and stay out of ``state_dict()``.
+    Under ``DistributedDataParallel`` the comm hook would reduce only the last micro-batch: data
+    parallelism with ``grad_accum > 1`` is ``ZeroAdamW``'s."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, overlap=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, grad_accum=1):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if int(grad_accum) != grad_accum or grad_accum < 1:
+            raise ValueError("grad_accum: a positive integer")
+        self.grad_accum = int(grad_accum)
+        self._micro = 0   # accumulate() calls since the last step()
+        self._acc = {}    # grad_accum > 1: parameter -> its fp32 accumulator
+        self._live = set()  # parameters whose accumulator holds a gradient of the current step
         self.overlap = overlap
         self._side = None
         self._clip = None  # gradclip.GlobalGradNorm: norm pass + result of the last clipped step
@@ -86,15 +101,50 @@ class MasterAdamW(torch.optim.Optimizer):
         return st
 
     @torch.no_grad()
+    def accumulate(self):
+        """End of one of the first N-1 backward passes of a step (``grad_accum=N``): fold every
+        ``.grad`` into its accumulator, on the current stream, and free it."""
+        if self.grad_accum == 1:
+            raise RuntimeError("MasterAdamW.accumulate(): constructed with grad_accum=1")
+        if self._micro >= self.grad_accum - 1:
+            raise RuntimeError(f"MasterAdamW.accumulate(): called {self._micro + 1} times with grad_accum="
+                               f"{self.grad_accum}; the last backward pass is followed by step()")
+        self._fold_all()
+        self._micro += 1
+
+    def _fold_all(self):
+        from .gradaccum import fold
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError(f"MasterAdamW: fp32/bf16 parameters only, got {p.dtype}")
+                acc = self._acc.get(p)
+                if acc is None:
+                    acc = self._acc[p] = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+                if not self._live and self._side is not None:
+                    # the first fold of a step overwrites what the last step's AdamW launches read
+                    torch.cuda.current_stream(p.device).wait_stream(self._side)
+                fold(acc, p.grad, p not in self._live)
+                self._live.add(p)
+                p.grad = None
+
+    @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.grad_accum > 1:
+            if self._micro != self.grad_accum - 1:
+                raise RuntimeError(f"MasterAdamW.step(): {self._micro} accumulate() calls since the last step, "
+                                   f"grad_accum={self.grad_accum} needs {self.grad_accum - 1}")
+            self._fold_all()  # the last micro-batch, on the compute stream (the side stream waits for it)
         side = None
         for group in self.param_groups:
             for p in group["params"]:
-                if self.overlap and p.is_cuda and p.grad is not None:
+                if self.overlap and p.is_cuda and (p.grad is not None or p in self._live):
                     if self._side is None:
                         self._side = torch.cuda.Stream(device=p.device)
                     side = self._side
@@ -107,6 +157,8 @@ class MasterAdamW(torch.optim.Optimizer):
         else:
             with torch.cuda.stream(side):
                 self._step_all(side)
+        self._live.clear()  # the accumulators are empty again (their memory is kept)
+        self._micro = 0
         return loss
 
     def _step_all(self, side):
@@ -114,10 +166,17 @@ class MasterAdamW(torch.optim.Optimizer):
         norm; then AdamW per parameter (on the GPU all on the current stream -- the side stream
         under overlap)."""
         clip = self._clip
+        scale = 1.0 / self.grad_accum  # the kernels round it to fp32
         work = []
         for group in self.param_groups:
             for p in group["params"]:
-                if p.grad is None:
+                if p in self._live:
+                    g = self._acc[p]
+                    if side is not None:
+                        g.record_stream(side)
+                    work.append((group, p, g))
+                    continue
+                if p.grad is None or self.grad_accum > 1:
                     continue
                 if p.dtype not in (torch.float32, torch.bfloat16):
                     raise TypeError(f"MasterAdamW: fp32/bf16 parameters only, got {p.dtype}")
@@ -136,7 +195,7 @@ class MasterAdamW(torch.optim.Optimizer):
         if clip is not None and work:
             if len({p.is_cuda for _, p, _ in work}) > 1:
                 raise ValueError("MasterAdamW(max_grad_norm): parameters on the GPU and on the CPU in one optimizer")
-            clip.run([(g, 1.0) for _, _, g in work if g.numel()])
+            clip.run([(g, scale) for _, _, g in work if g.numel()])
         for group, p, g in work:
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             st = self._state(p)
@@ -146,13 +205,15 @@ class MasterAdamW(torch.optim.Optimizer):
                 if clip is None:
                     g = self._hip_grad(p, g)  # a fix-up copy lives until this launch only
                 adamw_launch(master, st["exp_avg"], st["exp_avg_sq"], g, p if master is not p else None, p.numel(),
-                             st["step"], lr, b1, b2, eps, wd,
-                             clip=None if clip is None else (clip.out, clip.max_norm))
+                             st["step"], lr, b1, b2, eps, wd, scale,
+                             None if clip is None else (clip.out, clip.max_norm))
                 if side is not None:
                     ev = torch.cuda.Event()
                     ev.record(side)
                     p._pto_ready = ev
             else:
+                if self.grad_accum > 1:
+                    g = g * scale
                 self._step_reference(p, g if clip is None else g.float() * clip.coef, master, st, lr, b1, b2, eps, wd)
 
     @staticmethod

@@ -65,7 +65,8 @@ class _Sink:
 
 
 class _Bucket:
-    def __init__(self, params: List[nn.Parameter], world: int, rank: int, reduce_dtype=torch.float32):
+    def __init__(self, params: List[nn.Parameter], world: int, rank: int, reduce_dtype=torch.float32,
+                 accum: bool = False):
         self.params = params
         self.dtype = params[0].dtype
         dev = params[0].device
@@ -75,8 +76,19 @@ class _Bucket:
         self.lo = rank * self.shard
         self.flat_w = torch.zeros(self.npad, dtype=self.dtype, device=dev)
         # gradient bucket: the reduce dtype; at world 1 (nothing is reduced) the parameters' own
-        # dtype, i.e. exactly the .grad autograd would have produced
-        self.gdt = reduce_dtype if world > 1 else self.dtype
+        # dtype, i.e. exactly the .grad autograd would have produced.  Under gradient accumulation
+        # it is a per-backward staging buffer and takes the parameters' dtype as well: what is
+        # reduced is the fp32 accumulator (or its bf16 rounding), of dtype rdt
+        self.gdt = reduce_dtype if world > 1 and not accum else self.dtype
+        self.rdt = reduce_dtype if accum else self.gdt
+        # grad_accum > 1 only: the fp32 sum of the step's micro-batch gradients over the whole
+        # bucket (allocated by the first fold, then kept), the number of folds into it this step,
+        # the parameters that contributed to it, and the buffer a reduce-scatter in flight reads
+        self.accum = accum
+        self.acc: Optional[torch.Tensor] = None
+        self.nfold = 0
+        self.touched: set = set()
+        self.rs_src: Optional[torch.Tensor] = None
         self.n = n
         self.world = world
         # the full gradient bucket lives only from its first gradient of a backward to the end of
@@ -85,7 +97,7 @@ class _Bucket:
         # a step stays that of .grad-based training (the caching allocator recycles the block)
         self._g: Optional[torch.Tensor] = None
         self._dev = dev
-        self._gshard = None if world == 1 else torch.zeros(self.shard, dtype=self.gdt, device=dev)
+        self._gshard = None if world == 1 else torch.zeros(self.shard, dtype=self.rdt, device=dev)
         self.slot: Dict[int, int] = {}
         masters = torch.zeros(self.npad, dtype=torch.float32, device=dev) if self.dtype != torch.float32 else None
         off = 0
@@ -127,8 +139,11 @@ class _Bucket:
 
     @property
     def gshard(self) -> torch.Tensor:
-        # world 1: the shard IS the bucket (no reduce-scatter, no copy)
-        return self.grad32 if self.world == 1 else self._gshard
+        # world 1: the shard IS the bucket (no reduce-scatter, no copy) -- under gradient
+        # accumulation, the accumulator
+        if self.world > 1:
+            return self._gshard
+        return self.acc if self.accum else self.grad32
 
     def release_grad(self) -> None:
         self._g = None
@@ -148,11 +163,29 @@ class ZeroAdamW:
     rank the same bytes, hence the same clip factor.  Pass 2 is the per-bucket AdamW + all-gather
     loop, its kernel reading the sum on the device.  The global norm needs every bucket reduced
     before the first update, so the first weight all-gather starts one gradient read later than
-    without clipping; that is inherent to clipping by global norm."""
+    without clipping; that is inherent to clipping by global norm.
+
+    ``grad_accum=N`` (default 1: off, no accumulator exists): N backward passes per step, with
+    ``accumulate()`` after each of the first N-1 and ``step()`` after the last.  Every bucket gets a
+    persistent fp32 accumulator of the FULL bucket (``npad`` elements, 4 B per parameter on every
+    rank -- not the 1/W shard: that is the price of one collective per bucket per step instead of
+    one per micro-batch, DDP's ``no_sync``).  The per-backward bucket becomes a staging buffer in
+    the parameters' dtype whatever the reduce dtype, so a deposit is an exact copy and gradient
+    sinks serve every bf16 GPU bucket; when a micro-batch's last gradient of a bucket arrives, one
+    launch folds staging into the accumulator (``ops/gradaccum.py``: sequential fp32 sum) and the
+    staging buffer is released.  On the last micro-batch the accumulator is reduce-scattered (fp32
+    reduce), or the bf16 rounding of it that the same fold wrote (bf16 reduce; in place in a bf16
+    staging buffer); at world 1 the accumulator is the gradient shard.  The norm pass and AdamW
+    apply 1/(N*W) as their gradient scale."""
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  group=None, bucket_mb: float = 256.0, reduce_dtype=torch.float32, grad_view: bool = True,
-                 max_grad_norm=None):
+                 max_grad_norm=None, grad_accum=1):
+        if int(grad_accum) != grad_accum or grad_accum < 1:
+            raise ValueError("grad_accum: a positive integer")
+        self.grad_accum = int(grad_accum)
+        self._micro = 0  # accumulate() calls since the last step()
+        accum = self.grad_accum > 1
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -187,18 +220,20 @@ class ZeroAdamW:
         for p in reversed(params):
             cur = open_.setdefault(p.dtype, [])
             if cur and size[p.dtype] + p.numel() > cap:
-                self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype))
+                self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype, accum))
                 cur = open_[p.dtype] = []
                 size[p.dtype] = 0
             cur.append(p)
             size[p.dtype] = size.get(p.dtype, 0) + p.numel()
         for cur in open_.values():
             if cur:
-                self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype))
+                self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype, accum))
         self._of: Dict[int, _Bucket] = {id(p): b for b in self.buckets for p in b.params}
         for p in params:
             p.register_post_accumulate_grad_hook(self._on_grad)
         self.sinks = 0
+        for b in self.buckets:
+            b.unscaled = accum  # the accumulator holds the plain sum: AdamW applies 1/(N*W)
         if grad_view:
             for b in self.buckets:
                 if b.gdt != b.dtype or not b.flat_w.is_cuda:
@@ -226,8 +261,7 @@ class ZeroAdamW:
             return
         b = self._of[id(p)]
         if b.pending < 0:
-            raise RuntimeError("ZeroAdamW: a second backward before step() -- gradient accumulation "
-                               "across backward passes is not supported (the bucket was already reduced)")
+            raise RuntimeError(self._second_backward())
         off = b.slot[id(p)]
         self._deposit(b.grad32[off:off + p.numel()], p.grad.reshape(-1), b.unscaled)
         p.grad = None
@@ -235,15 +269,82 @@ class ZeroAdamW:
 
     def _arrive(self, b: _Bucket, p: torch.Tensor) -> None:
         if b.pending < 0:
-            raise RuntimeError("ZeroAdamW: a second backward before step() -- gradient accumulation "
-                               "across backward passes is not supported (the bucket was already reduced)")
+            raise RuntimeError(self._second_backward())
         if id(p) in b.arrived:
             raise RuntimeError("ZeroAdamW: a parameter received two gradients in one backward (a weight "
                                "used twice cannot write its gradient in place; construct with grad_view=False)")
         b.arrived.add(id(p))
         b.pending -= 1
         if b.pending == 0:
-            self._reduce_scatter(b)
+            if b.accum:
+                self._fold(b)
+            else:
+                self._reduce_scatter(b)
+
+    def _second_backward(self) -> str:
+        if self.grad_accum > 1:
+            return ("ZeroAdamW: a second backward before accumulate() / step() (grad_accum="
+                    f"{self.grad_accum}: the bucket was already folded for this micro-batch)")
+        return ("ZeroAdamW: a second backward before step() -- gradient accumulation "
+                "across backward passes is not supported (the bucket was already reduced) "
+                "without grad_accum > 1")
+
+    def _fold(self, b: _Bucket) -> None:
+        """grad_accum > 1: every gradient of this micro-batch is in the staging bucket -- fold it
+        into the accumulator (one launch) and release it; on the last micro-batch start the
+        bucket's one reduce-scatter of the step."""
+        from ..ops.gradaccum import fold
+        last = self._micro == self.grad_accum - 1
+        stage = b.grad32
+        if b.acc is None:
+            b.acc = torch.empty(b.npad, dtype=torch.float32, device=stage.device)
+        out = None
+        if last and self.world > 1 and b.rdt == torch.bfloat16:
+            # the bf16 reduce sends the rounded sum: in place in a bf16 staging bucket
+            out = stage if stage.dtype == torch.bfloat16 else torch.empty_like(stage, dtype=torch.bfloat16)
+        fold(b.acc, stage, b.nfold == 0, out)
+        b.nfold += 1
+        b.touched |= b.arrived
+        b.release_grad()
+        b.pending = -1  # folded for this micro-batch (accumulate() / step() reopen the bucket)
+        if last and self.world > 1:
+            b.rs_src = b.acc if out is None else out
+            b.rs_work = dist.reduce_scatter_tensor(b._gshard, b.rs_src, group=self.group, async_op=True)
+
+    def _fill_missing(self, b: _Bucket, force: bool) -> bool:
+        """Staging slots of the parameters without a gradient from this backward: a ``.grad`` set
+        outside backward is deposited, the rest zeroed.  A bucket no gradient reached at all is
+        left alone (returns False) unless ``force``: then it is all zeros."""
+        late = [p for p in b.params if id(p) not in b.arrived]
+        if not force and not b.arrived and all(p.grad is None for p in late):
+            return False
+        for p in late:
+            slot = b.grad32[b.slot[id(p)]:b.slot[id(p)] + p.numel()]
+            if p.grad is None:
+                slot.zero_()
+            else:
+                self._deposit(slot, p.grad.reshape(-1), b.unscaled)
+                p.grad = None
+                b.arrived.add(id(p))
+        return True
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """End of one of the first N-1 backward passes of a step (``grad_accum=N``): buckets that
+        some parameter did not reach are folded with what arrived (a missing gradient adds
+        nothing), and every bucket is reopened for the next micro-batch."""
+        if self.grad_accum == 1:
+            raise RuntimeError("ZeroAdamW.accumulate(): constructed with grad_accum=1")
+        if self._micro >= self.grad_accum - 1:
+            raise RuntimeError(f"ZeroAdamW.accumulate(): called {self._micro + 1} times with grad_accum="
+                               f"{self.grad_accum}; the last backward pass is followed by step()")
+        for b in self.buckets:
+            if b.pending >= 0:
+                if self._fill_missing(b, False):
+                    self._fold(b)
+            b.pending = len(b.params)
+            b.arrived.clear()
+        self._micro += 1
 
     def _deposit(self, dst: torch.Tensor, g: torch.Tensor, unscaled: bool = False) -> None:
         """dst = g / W in the bucket dtype -- the comm hooks' ``grad / W`` before the sum.  For a
@@ -278,10 +379,24 @@ class ZeroAdamW:
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._micro != self.grad_accum - 1:
+            raise RuntimeError(f"ZeroAdamW.step(): {self._micro} accumulate() calls since the last step, "
+                               f"grad_accum={self.grad_accum} needs {self.grad_accum - 1}")
         self.t += 1
         skip: Dict[int, set] = {}
         for b in self.buckets:
-            if b.pending >= 0:
+            if b.accum:
+                # stragglers of the last micro-batch: fold what arrived (zeros where nothing ever
+                # did, so the accumulator is defined); at world 1 a parameter without a gradient
+                # in any micro-batch is left untouched
+                if b.pending >= 0:
+                    self._fill_missing(b, True)
+                    self._fold(b)
+                if self.world == 1:
+                    missing = {id(p) for p in b.params} - b.touched
+                    if missing:
+                        skip[id(b)] = missing
+            elif b.pending >= 0:
                 # some parameter of this bucket got no gradient through the hook this step.  Only
                 # the slots that never arrived are filled (zeros, or a gradient set outside
                 # backward); deposited gradients are kept.  At world > 1 a missing gradient
@@ -302,8 +417,7 @@ class ZeroAdamW:
                 self._reduce_scatter(b)
         if self._clip is not None:
             # pass 1 of a clipped step: global norm of the averaged gradient, left on the device
-            self._clip.run([(self._reduced(b), 1.0 / self.world if b.unscaled else 1.0)
-                            for b in reversed(self.buckets)])
+            self._clip.run([(self._reduced(b), self._gscale(b)) for b in reversed(self.buckets)])
         # forward order (the last bucket holds the first layers): their all-gathers go first
         for b in reversed(self.buckets):
             self._reduced(b)
@@ -332,7 +446,15 @@ class ZeroAdamW:
                 b.ag_work = dist.all_gather_into_tensor(b.flat_w, src, group=self.group, async_op=True)
             b.pending = len(b.params)
             b.arrived.clear()
+            b.nfold = 0  # the accumulator is empty again (its memory is kept)
+            b.touched.clear()
+        self._micro = 0
         return loss
+
+    def _gscale(self, b: _Bucket) -> float:
+        """What the norm pass and AdamW multiply this bucket's gradient by: 1/(N*W) for a plain
+        sum over micro-batches and ranks, 1 where the deposit scaled already."""
+        return 1.0 / (self.grad_accum * self.world) if b.unscaled else 1.0
 
     def _reduced(self, b: _Bucket) -> torch.Tensor:
         """The bucket's gradient shard, its reduce-scatter waited for.  At world > 1 the full
@@ -343,6 +465,7 @@ class ZeroAdamW:
             b.rs_work = None
         if self.world > 1:
             b.release_grad()
+            b.rs_src = None
         return b.gshard
 
     def last_grad_norm(self):
@@ -378,11 +501,15 @@ class ZeroAdamW:
         clip = self._clip
         if w.is_cuda:
             adamw_launch(master, b.exp_avg, b.exp_avg_sq, b.gshard, w if b.master is not None else None, b.shard, t,
-                         self.lr, b1, b2, self.eps, self.weight_decay, 1.0 / self.world if b.unscaled else 1.0,
+                         self.lr, b1, b2, self.eps, self.weight_decay, self._gscale(b),
                          None if clip is None else (clip.out, clip.max_norm))
         else:
             st = {"step": t, "exp_avg": b.exp_avg, "exp_avg_sq": b.exp_avg_sq}
-            g = b.gshard if clip is None else b.gshard.float() * clip.coef
+            g = b.gshard
+            if b.accum:
+                g = g.float() * self._gscale(b)
+            if clip is not None:
+                g = g.float() * clip.coef
             MasterAdamW._step_reference(w, g, master, st, self.lr, b1, b2, self.eps, self.weight_decay)
 
     def _wait_weights(self, buckets) -> None:
