@@ -77,6 +77,21 @@ __device__ __forceinline__ void stamp(u64* dbg, int phase, int thread = 0) {
     dbg[blk * 16 + 8 + phase] = (u64)clock64();  // shader clock -> effective GHz per phase
   }
 }
+// Stamp 0 ("block start") of the five step kernels, in two halves (round 7): entry_clock() reads
+// both clocks as the kernel's first instructions -- they need no kernel argument -- and
+// stamp_entry() stores them once the kernel's first vector loads are issued.  Testing `dbg`
+// ahead of those loads (as stamp(dbg, 0) does) puts a wait on the argument read in front of them.
+struct EntryClock {
+  u64 wall, shader;
+};
+__device__ __forceinline__ EntryClock entry_clock() { return EntryClock{(u64)wall_clock64(), (u64)clock64()}; }
+__device__ __forceinline__ void stamp_entry(u64* dbg, const EntryClock& t0) {
+  if (dbg != nullptr && threadIdx.x == 0) {
+    const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    dbg[blk * 16] = t0.wall;
+    dbg[blk * 16 + 8] = t0.shader;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // A: conv1 forward (+bias, ReLU, 2x2 max-pool with argmax).  One thread per
@@ -492,12 +507,17 @@ __device__ __forceinline__ void conv12_store_w2(float* w_s, const float4 (&wq)[2
   }
 }
 
+// Parameter order (round 7): the first 14 dwords -- what the command processor preloads into
+// SGPRs -- are the pointers the staging loads go through; then what else the prologue reads
+// (adjacent in the argument block), the gather source of the unstaged path, and the epilogue's
+// outputs.  `cursor`, `scale` and `shift` are src's, hoisted.
 __global__ __launch_bounds__(AB_NT) void conv12_fwd_kernel(
-    BatchSrc src, const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ a1,
-    uint8_t* __restrict__ idx1, float* __restrict__ xn_out, int* __restrict__ lab_out,
-    float* __restrict__ a2, uint8_t* __restrict__ idx2, int B, const uint8_t* __restrict__ stg_x,
-    const int* __restrict__ stg_lab, const int* __restrict__ stg_tag, u64* dbg) {
+    const uint8_t* __restrict__ stg_x, const int* __restrict__ stg_tag, const int* __restrict__ cursor,
+    const float* __restrict__ w, const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ bias, const int* __restrict__ stg_lab, u64* dbg, float scale, float shift, int B,
+    BatchSrc src, float* __restrict__ a1, uint8_t* __restrict__ idx1, float* __restrict__ xn_out,
+    int* __restrict__ lab_out, float* __restrict__ a2, uint8_t* __restrict__ idx2) {
+  const EntryClock t0 = entry_clock();
   __shared__ float img[28 * AB_IRS];
   __shared__ float w1s[W1B + 20];
   __shared__ __align__(16) float in_s[C2_IMG];
@@ -505,7 +525,6 @@ __global__ __launch_bounds__(AB_NT) void conv12_fwd_kernel(
   __shared__ f32x4 red[3][4][64];
   __shared__ __align__(16) uint8_t id1_s[20 * 144];  // conv1 pool argmax (published per channel group)
   const int cg = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  stamp(dbg, 0);
   const bool pub = cg == 0;  // xn and lab
   // conv2 epilogue bias, loaded with the staging loads (no round trip after the last barrier)
   const int co_pre = cg * 16 + (tid & 15);
@@ -513,21 +532,18 @@ __global__ __launch_bounds__(AB_NT) void conv12_fwd_kernel(
   float4 wq[2];
   {
     // the batch: from the staging buffer the previous step's fc1_bwd filled (one load, no
-    // cursor -> permutation -> pixel chain) when its tag is this step's cursor, else gathered
-    float x0;
+    // cursor -> permutation -> pixel chain) when its tag is this step's cursor, else gathered.
+    // The staged pixel and the weights are loaded through preloaded pointers alone, ahead of the
+    // tag test: that test waits on two scalar loads from memory (and, with them, on the rest of
+    // the argument block), which the vector loads now overlap instead of following (round 7).
+    float x0 = 0.f;
     int lab = 0;
-    if (stg_x != nullptr) {
-      x0 = (float)stg_x[(size_t)b * 784 + min(tid, 783)] * src.scale + src.shift;
-      lab = stg_lab[b];
-      if (stg_tag[0] != src.cursor[0]) {  // block-uniform
-        const int row = batch_row(src, b, B);
-        x0 = load_px(src, row, min(tid, 783));
-        if (src.labels != nullptr) lab = src.labels[row];
-      }
-    } else {
-      const int row = batch_row(src, b, B);
-      x0 = load_px(src, row, min(tid, 783));
-      if (src.labels != nullptr) lab = src.labels[row];
+    const bool staged = stg_x != nullptr;
+    int tag = 0, cur = 0;
+    if (staged) {
+      x0 = (float)stg_x[(size_t)b * 784 + min(tid, 783)];
+      tag = stg_tag[0];
+      cur = cursor[0];
     }
     const float wv = w1[min(tid, 499)];
     const float bv1 = b1[min(tid, 19)];
@@ -539,6 +555,21 @@ __global__ __launch_bounds__(AB_NT) void conv12_fwd_kernel(
       const int j = e / 125, q = e - j * 125;
       const int co = min(cg * 16 + j, 49);
       wq[k] = reinterpret_cast<const float4*>(w + (size_t)co * 500)[q];
+    }
+    if (staged) {
+      // a vector load (through a zero the compiler cannot see): as a scalar load its wait would
+      // stand between the argument read and the tag test
+      int z = 0;
+      asm("" : "+v"(z));
+      lab = stg_lab[b + z];
+    }
+    stamp_entry(dbg, t0);
+    x0 = x0 * scale + shift;
+    asm volatile("" : "+s"(tag), "+s"(cur));  // the compare (and its wait) stays below the loads
+    if (!staged || tag != cur) {  // block-uniform
+      const int row = batch_row(src, b, B);
+      x0 = load_px(src, row, min(tid, 783));
+      if (src.labels != nullptr) lab = src.labels[row];
     }
     if (tid < 784) img[(tid / 28) * AB_IRS + tid % 28] = x0;
     if (tid < 500) w1s[tid + tid / 25] = wv;  // (tid / 25) * W1R + tid % 25 with W1R = 26
@@ -639,10 +670,10 @@ __global__ __launch_bounds__(640 / KS) void fc1_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
     float* __restrict__ h, int B, u64* dbg) {
   static_assert(KS == 1 || KS == 2, "fc1: 10 or 5 waves of 80 K each");
+  const EntryClock t0 = entry_clock();
   constexpr int NW = 10 / KS;
   __shared__ f32x4 red[NW][64];
   const int nt = blockIdx.x, mt = blockIdx.y, kz = blockIdx.z, tid = threadIdx.x;
-  stamp(dbg, 0);
   const int lane = tid & 63, wv = tid >> 6;
   const int i = lane & 15, g = lane >> 4;
   const int row = mt * 16 + i, col = nt * 16 + i;
@@ -657,6 +688,7 @@ __global__ __launch_bounds__(640 / KS) void fc1_fwd_kernel(
   const int l_e = tid >> 2, r_e = tid & 3;
   const int orow = mt * 16 + (l_e >> 4) * 4 + r_e, ocol = nt * 16 + (l_e & 15);
   const float bo = (bias != nullptr && tid < 256 && ocol < 500) ? bias[ocol] : 0.f;
+  stamp_entry(dbg, t0);
   f32x4 c0 = zero4(), c1 = zero4();
 #pragma unroll
   for (int s = 0; s < 5; ++s) {
@@ -1112,18 +1144,19 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_kernel(Fc1Bwd a, u64* dbg) {
 // per-sample (loss, correct), the kt = 1..8 blocks one wave's dh columns each, for the tail
 // (dW_fc1, dW_fc2, statistics).  Sums differ from
 // head_kernel's lane-tree order by fp32 rounding (the DDP paths keep head + fc1_bwd).
-struct Fc1BwdHead {
-  const float *hp0, *hp1;       // fc1 split-K partials [B][500] x 2 (hp0 includes fc1.bias)
-  const float *w2, *b2;         // fc2.weight [10][500], fc2.bias [10]
-  const int* lab;               // [B]
-  const float* a2;              // [B][800]
-  const uint8_t* idx2;          // [B][800]
-  const float* w1;              // fc1.weight [500][800]
-  float* dz2;                   // [B][50][8][8] (dense), or
-  float* dpool;                 // [B][800] pooled d(a2) (conv_bwd4 un-pools it through idx2)
-  float *h_out, *dh_out, *dlog_out, *per_sample;  // published by the kt == 0 (dh: 1..8) blocks
-  float grad_scale;             // 1 / B
-  int B;
+// Kernel parameters (round 7), all plain but the staging blocks' own:
+//   hp0, hp1   fc1 split-K partials [B][500] x 2 (hp0 includes fc1.bias)
+//   w2, w1     fc2.weight [10][500], fc1.weight [500][800]
+//   a2         [B][800]
+//   dbg, B, grad_scale (1 / B) -- to here: the 14 dwords preloaded into SGPRs, what the tile
+//                                 blocks' staging loads go through
+//   idx2 [B][800], lab [B], b2 (fc2.bias [10]), h_out    the rest of what the prologue reads
+//              (the loads through them are the last of the prologue's)
+//   dpool      [B][800] pooled d(a2) (conv_bwd4 un-pools it through idx2), or
+//   dz2        [B][50][8][8] (dense)
+//   dh_out, dlog_out, per_sample   published by the kt == 0 (dh: 1..8) blocks
+// The trailing struct is read by the staging blocks alone.
+struct Fc1BwdStage {
   BatchSrc nsrc;                // next-batch staging (stage_x != null), as fc1_bwd
   int stage_adv;
   uint8_t* stage_x;
@@ -1149,7 +1182,11 @@ __device__ __forceinline__ int dsx(int row, int col) { return row * H_DS + col; 
 // float4 entry of staging pass q (0-3) for thread tid: rows 0-7 in passes 0-1, rows 8-15 in 2-3
 __device__ __forceinline__ int stage_e(int q, int tid) { return q < 2 ? tid + q * E_NT : 1000 + tid + (q - 2) * E_NT; }
 
-__global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* dbg) {
+__global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(
+    const float* hp0, const float* hp1, const float* w2, const float* w1, const float* a2, u64* dbg, int B,
+    float grad_scale, const uint8_t* idx2, const int* lab, const float* b2, float* h_out, float* dpool,
+    float* dz2, float* dh_out, float* dlog_out, float* per_sample, Fc1BwdStage a) {
+  const EntryClock t0 = entry_clock();
   __shared__ __align__(16) float hs[16 * H_RS];
   __shared__ __align__(16) float w2s[16 * H_RS];
   __shared__ __align__(16) float dhs[16 * H_DS];
@@ -1158,10 +1195,12 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* d
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
-  const int B = a.B;
   const int nmt = (B + 15) / 16;
   const int nJ2 = nmt * 50;
-  stamp(dbg, 0);
+  // (`dbg` is one of the preloaded arguments here: testing it at once waits on nothing.  Storing
+  // stamp 0 after the loads instead changes this kernel's VGPR allocation from 112 to 104, which
+  // the co-residency rows of tests/test_kernel_resources.py pin.)
+  stamp_entry(dbg, t0);
   if ((int)blockIdx.x >= nJ2) {  // next-batch staging (fc1_bwd's staging blocks)
     const int j4 = blockIdx.x - nJ2;
     const long long step = (long long)a.nsrc.cursor[0] + a.stage_adv;
@@ -1196,32 +1235,32 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* d
   for (int q = 0; q < 4; ++q) {
     const int e = min(stage_e(q, tid), 1999), row = e / 125, c4 = e - row * 125;
     const size_t o = (size_t)min(mt * 16 + row, B - 1) * 500 + 4 * c4;
-    const float4 x0 = *reinterpret_cast<const float4*>(a.hp0 + o);
-    const float4 x1 = *reinterpret_cast<const float4*>(a.hp1 + o);
+    const float4 x0 = *reinterpret_cast<const float4*>(hp0 + o);
+    const float4 x1 = *reinterpret_cast<const float4*>(hp1 + o);
     // head_kernel's h: relu(part0 + part1), the bias folded into part0 by fc1_fwd
     hq[q] = make_float4(fmaxf(x0.x + x1.x, 0.f), fmaxf(x0.y + x1.y, 0.f), fmaxf(x0.z + x1.z, 0.f),
                         fmaxf(x0.w + x1.w, 0.f));
   }
   float4 wq[3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) wq[q] = reinterpret_cast<const float4*>(a.w2)[min(stage_e(q, tid), 1249)];
+  for (int q = 0; q < 3; ++q) wq[q] = reinterpret_cast<const float4*>(w2)[min(stage_e(q, tid), 1249)];
   const int kb = 64 * wv + 16 * g;  // the dz2 job's K range of this lane
   float bv[16];
 #pragma unroll
-  for (int s = 0; s < 16; ++s) bv[s] = a.w1[(size_t)min(kb + s, 499) * 800 + kt * 16 + i];
+  for (int s = 0; s < 16; ++s) bv[s] = w1[(size_t)min(kb + s, 499) * 800 + kt * 16 + i];
   const int l_e = (tid & 255) >> 2, r_e = tid & 3;
   const int bs = mt * 16 + (l_e >> 4) * 4 + r_e;
   const int ff = kt * 16 + (l_e & 15);
   const size_t oe = (size_t)min(bs, B - 1) * 800 + ff;
-  float a2o = a.a2[oe];
-  int pidx = a.idx2[oe];
+  float a2o = a2[oe];
+  int pidx = idx2[oe];
   // softmax lanes (waves 0-3): sample 4 wv + (lane >> 4), class lane & 15
   const int sm_s = 4 * wv + (lane >> 4), sm_j = lane & 15;
   int lab_t = 0;
   float b2v = 0.f;
   if (tid < 256) {
-    lab_t = a.lab[min(mt * 16 + sm_s, B - 1)];
-    b2v = a.b2[min(sm_j, 9)];
+    lab_t = lab[min(mt * 16 + sm_s, B - 1)];
+    b2v = b2[min(sm_j, 9)];
   }
   // ---- h and W2 into LDS (zero rows / columns pad K to 512 and N to 16)
 #pragma unroll
@@ -1233,7 +1272,7 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* d
       const float4 h4 = rv ? hq[q] : make_float4(0.f, 0.f, 0.f, 0.f);
       *reinterpret_cast<float4*>(hs + row * H_RS + 4 * c4) =
           q >= 2 ? make_float4(h4.z, h4.w, h4.x, h4.y) : h4;  // hsx: columns ^ 2 in rows 8-15
-      if (pub && rv) reinterpret_cast<float4*>(a.h_out + (size_t)(mt * 16 + row) * 500)[c4] = h4;
+      if (pub && rv) reinterpret_cast<float4*>(h_out + (size_t)(mt * 16 + row) * 500)[c4] = h4;
     }
   }
 #pragma unroll
@@ -1301,13 +1340,13 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* d
     PTO_ROW_STEP(0xB1) PTO_ROW_STEP(0x4E) PTO_ROW_STEP(0x141) PTO_ROW_STEP(0x140)
 #undef PTO_ROW_STEP
     const float lse = mx + __logf(se);
-    const float dl = (jv && sv) ? (__expf(logit - lse) - (sm_j == lab_t ? 1.f : 0.f)) * a.grad_scale : 0.f;
+    const float dl = (jv && sv) ? (__expf(logit - lse) - (sm_j == lab_t ? 1.f : 0.f)) * grad_scale : 0.f;
     dls[sm_s][sm_j] = dl;
     if (pub && sv) {
-      if (jv) a.dlog_out[(size_t)smp * 10 + sm_j] = dl;
+      if (jv) dlog_out[(size_t)smp * 10 + sm_j] = dl;
       if (sm_j == 0) {
-        a.per_sample[2 * smp] = lse - lt;
-        a.per_sample[2 * smp + 1] = pr == lab_t ? 1.f : 0.f;
+        per_sample[2 * smp] = lse - lt;
+        per_sample[2 * smp + 1] = pr == lab_t ? 1.f : 0.f;
       }
     }
   }
@@ -1377,7 +1416,7 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* d
     for (int it = 0; it < 4; ++it) {
       const int e = lane + 64 * it, row = e >> 4, col = 64 * wv + 4 * (e & 15);
       if (col < 500 && mt * 16 + row < B)
-        *reinterpret_cast<float4*>(a.dh_out + (size_t)(mt * 16 + row) * 500 + col) =
+        *reinterpret_cast<float4*>(dh_out + (size_t)(mt * 16 + row) * 500 + col) =
             *reinterpret_cast<const float4*>(dhs + dsx(row, col));
     }
   }
@@ -1387,11 +1426,11 @@ __global__ __launch_bounds__(E_NT) void fc1_bwd_head_kernel(Fc1BwdHead a, u64* d
   for (int q = 1; q < E_NW; ++q) v += red[q][l_e][r_e];
   if (tid < 256 && bs < B) {
     const float d = a2o > 0.f ? v : 0.f;
-    if (a.dpool != nullptr) {
-      a.dpool[(size_t)bs * 800 + ff] = d;
+    if (dpool != nullptr) {
+      dpool[(size_t)bs * 800 + ff] = d;
     } else {
       const int co = ff >> 4, ph = (ff >> 2) & 3, pw = ff & 3;
-      float* z = a.dz2 + (size_t)bs * 3200 + co * 64 + (2 * ph) * 8 + 2 * pw;
+      float* z = dz2 + (size_t)bs * 3200 + co * 64 + (2 * ph) * 8 + 2 * pw;
       z[0] = pidx == 0 ? d : 0.f;
       z[1] = pidx == 1 ? d : 0.f;
       z[8] = pidx == 2 ? d : 0.f;
@@ -1888,8 +1927,10 @@ __device__ __forceinline__ f32x4 bwd4_2b(const float* dzc_s, const float* a1c_s,
 __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
     const float* __restrict__ dp, const uint8_t* __restrict__ ip,
     const float* __restrict__ w2, const float* __restrict__ a1,
-    const uint8_t* __restrict__ idx1, const float* __restrict__ xn, float* __restrict__ slab,
-    int stride, int o_gw2, int o_gb2, int o_gw1, int o_gb1, int B, u64* dbg) {
+    const uint8_t* __restrict__ idx1, const float* __restrict__ xn, int B, int stride,
+    float* __restrict__ slab, int o_gw2, int o_gb2, int o_gw1, int o_gb1, u64* dbg) {
+  // (the six staged operands, B and stride: the 14 preloaded dwords; the slab is the epilogue's)
+  const EntryClock t0 = entry_clock();
   extern __shared__ float lds[];
   float* dzc_s = lds + G_OFF_DZ;
   float* w_s = lds + G_OFF_W;
@@ -1913,7 +1954,6 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
   // -cig shift puts every whole 4-column group on a 16-byte slab boundary (epilogue float4s)
   const int jbase = 32 * r - cig;
   const int c0 = max(jbase, 0) / 25;  // first of the <= 2 input channels those columns touch
-  stamp(dbg, 0);
 
   // ---- phase 1: stage.  dz2 arrives pooled -- d(a2) [B][800] (ReLU-masked) + conv12's pool
   // argmax idx2 [B][800] -- and is un-pooled into the LDS image of the chunk's 4 samples (3.2 KB
@@ -1943,6 +1983,7 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
   if (e_av >= 0 && e_av < 180) avv = reinterpret_cast<const float4*>(a1)[(size_t)bo * 720 + cig * 180 + e_av];
   if (e_x >= 0 && e_x < 196) xvv = reinterpret_cast<const float4*>(xn)[(size_t)bo * 196 + e_x];
   if (tid < 45) ivv = reinterpret_cast<const uint4*>(idx1)[(size_t)bo * 180 + cig * 45 + tid];
+  stamp_entry(dbg, t0);
   __shared__ unsigned s_grp[2];  // group arrival counters (waves 0-7, waves 8-15)
   if (tid == 0) {
     s_grp[0] = 0u;
@@ -2324,47 +2365,88 @@ __device__ __forceinline__ void tail_w1_tile(const TailW1& tw, int tile, int lan
   }
 }
 
+// Kernel parameters (round 7).  Leading, plain -- the 14 dwords preloaded into SGPRs: the block
+// dispatch (tw_blocks, red_blocks), what the fc1.weight tiles (400 of the 609 blocks at B = 64,
+// dispatched first) load through -- dh, a2, fc1's parameters and momentum, B, grad_only -- and the
+// slab.  TailArgs has the rest in the order the blocks read it: the reduction blocks' geometry and
+// parameters, the fc2 tiles' operands, the hyper-parameters, then what only epilogues touch.
+struct TailArgs {
+  int n, stride;
+  SlabRows sr;
+  float *p, *buf;                         // conv parameters / momentum of the reduced columns
+  const float *dlog, *h, *per_sample;     // TailW1's fc2 members
+  float *p2w, *m2w, *pb2, *mb2;
+  int fc2;
+  float loss_scale;
+  SgdHyper hy;
+  float *w1g, *g2w, *gb2, *stats, *gout;  // gradient outputs (optional) and the statistics
+  int* step_counter;
+  float* p2;                              // plain SGD range
+  const float* g2;
+  float* buf2;
+  int n2;
+};
+
 __global__ __launch_bounds__(256) void slab_reduce_sgd_kernel(
-    const float* __restrict__ P, SlabRows sr, int n, int stride, float* __restrict__ gout,
-    float* __restrict__ p, float* __restrict__ buf, SgdHyper hy, int* __restrict__ step_counter,
-    float* __restrict__ p2, const float* __restrict__ g2, float* __restrict__ buf2, int n2,
-    int red_blocks, TailW1 tw, u64* dbg) {
+    const float* __restrict__ tw_dh, const float* __restrict__ tw_a2, float* __restrict__ tw_p,
+    float* __restrict__ tw_m, const float* __restrict__ P, int tw_blocks, int red_blocks, int tw_B,
+    int grad_only, TailArgs ta, u64* dbg) {
+  const EntryClock t0 = entry_clock();
   __shared__ float4 red[SR_SL][SR_COLS];
-  stamp(dbg, 0);
   const int tid = threadIdx.x;
-  // logical block ids: [0, red_blocks) the slab reduction, [red_blocks, + tw.blocks) the
+  // logical block ids: [0, red_blocks) the slab reduction, [red_blocks, + tw_blocks) the
   // fc1.weight tiles, then the plain SGD range.  Dispatch order: the fc1.weight tiles first
   // (same-box A/B against reduction-first: 38.49-38.63 vs 38.60-38.77 us/step at K = 2000,
   // profiles/r5_tail/ab.txt)
-  const int blk = (int)blockIdx.x < tw.blocks ? (int)blockIdx.x + red_blocks
-                  : (int)blockIdx.x < tw.blocks + red_blocks ? (int)blockIdx.x - tw.blocks : (int)blockIdx.x;
-  if (blk >= red_blocks && blk < red_blocks + tw.blocks) {
+  const int blk = (int)blockIdx.x < tw_blocks ? (int)blockIdx.x + red_blocks
+                  : (int)blockIdx.x < tw_blocks + red_blocks ? (int)blockIdx.x - tw_blocks : (int)blockIdx.x;
+  // Each kind of block reads the members of `ta` it needs itself; the dispatch above and the
+  // fc1.weight tiles' loads go through preloaded arguments alone.
+  if (blk >= red_blocks && blk < red_blocks + tw_blocks) {
     const int tile = (blk - red_blocks) * 4 + (tid >> 6);
-    if (tile < 1600) tail_w1_tile(tw, tile, tid & 63, hy);
-    else tail_fc2_tile(tw, tile - 1600, tid & 63, hy);
+    TailW1 tw{};
+    tw.dh = tw_dh; tw.a2 = tw_a2; tw.p = tw_p; tw.m = tw_m; tw.B = tw_B; tw.blocks = tw_blocks;
+    tw.grad_only = grad_only;
+    if (tile < 1600) {
+      tw.g = ta.w1g;
+      tail_w1_tile(tw, tile, tid & 63, ta.hy);
+    } else {
+      tw.fc2 = ta.fc2; tw.dlog = ta.dlog; tw.h = ta.h; tw.per_sample = ta.per_sample; tw.stats = ta.stats;
+      tw.loss_scale = ta.loss_scale; tw.p2 = ta.p2w; tw.m2 = ta.m2w; tw.g2 = ta.g2w; tw.pb2 = ta.pb2;
+      tw.mb2 = ta.mb2; tw.gb2 = ta.gb2;
+      tail_fc2_tile(tw, tile - 1600, tid & 63, ta.hy);
+    }
+    stamp_entry(dbg, t0);
     stamp(dbg, 1);
     return;
   }
   if (blk >= red_blocks) {
     // plain SGD over the second range (already-reduced grads, e.g. the fc bucket)
-    const int v = (blk - red_blocks - tw.blocks) * 256 + tid;
-    if (v < (n2 >> 2)) {
-      float4 pp = reinterpret_cast<float4*>(p2)[v];
-      const float4 gg = reinterpret_cast<const float4*>(g2)[v];
-      float4 bb = reinterpret_cast<float4*>(buf2)[v];
-      sgd4(pp, bb, gg, hy);
-      reinterpret_cast<float4*>(p2)[v] = pp;
-      reinterpret_cast<float4*>(buf2)[v] = bb;
+    const int v = (blk - red_blocks - tw_blocks) * 256 + tid;
+    if (v < (ta.n2 >> 2)) {
+      float4 pp = reinterpret_cast<float4*>(ta.p2)[v];
+      const float4 gg = reinterpret_cast<const float4*>(ta.g2)[v];
+      float4 bb = reinterpret_cast<float4*>(ta.buf2)[v];
+      sgd4(pp, bb, gg, ta.hy);
+      reinterpret_cast<float4*>(ta.p2)[v] = pp;
+      reinterpret_cast<float4*>(ta.buf2)[v] = bb;
     }
+    stamp_entry(dbg, t0);
     stamp(dbg, 1);
     return;
   }
+  const SlabRows sr = ta.sr;
+  const int n = ta.n, stride = ta.stride;
+  float* __restrict__ const gout = ta.gout;
+  float* __restrict__ const p = ta.p;
+  float* __restrict__ const buf = ta.buf;
+  int* const step_counter = ta.step_counter;
   const int col = blk * SR_COLS + (tid % SR_COLS);
   const int slice = tid / SR_COLS;
   const int n4 = n >> 2;
   const int cc = min(col, n4 - 1);
   float4 pp = make_float4(0.f, 0.f, 0.f, 0.f), bb = pp;
-  if (tid < SR_COLS && !tw.grad_only) {  // prefetch the parameters + momentum this column updates
+  if (tid < SR_COLS && !grad_only) {  // prefetch the parameters + momentum this column updates
     pp = reinterpret_cast<const float4*>(p)[cc];
     bb = reinterpret_cast<const float4*>(buf)[cc];
   }
@@ -2376,13 +2458,14 @@ __global__ __launch_bounds__(256) void slab_reduce_sgd_kernel(
 #pragma unroll
     for (int q = 1; q < SR_SL; ++q) add4(r, red[q][tid]);
     if (gout != nullptr) reinterpret_cast<float4*>(gout)[col] = r;
-    if (!tw.grad_only) {
-      sgd4(pp, bb, r, hy);
+    if (!grad_only) {
+      sgd4(pp, bb, r, ta.hy);
       reinterpret_cast<float4*>(p)[col] = pp;
       reinterpret_cast<float4*>(buf)[col] = bb;
     }
   }
   if (step_counter != nullptr && blk == 0 && tid == 0) atomicAdd(step_counter, 1);
+  stamp_entry(dbg, t0);
   stamp(dbg, 1);
 }
 
@@ -2571,8 +2654,8 @@ int pto_mnist_conv12_fwd(const void* x, int is_u8, const int* labels, const int*
                            !is_u8 || labels == nullptr))
     return -1;
   const BatchSrc src = make_src(x, is_u8, labels, perm, cursor, host_offset, n_total, scale, shift);
-  hipLaunchKernelGGL(conv12_fwd_kernel, dim3(4, B), dim3(AB_NT), 0, (hipStream_t)stream, src, w1, b1, w2, b2,
-                     a1, idx1, xn_out, lab_out, a2, idx2, B, stg_x, stg_lab, stg_tag, dbg_next());
+  hipLaunchKernelGGL(conv12_fwd_kernel, dim3(4, B), dim3(AB_NT), 0, (hipStream_t)stream, stg_x, stg_tag, cursor,
+                     w2, w1, b1, b2, stg_lab, dbg_next(), scale, shift, B, src, a1, idx1, xn_out, lab_out, a2, idx2);
   return (int)hipGetLastError();
 }
 
@@ -2750,6 +2833,21 @@ int pto_sgd_momentum(float* p, const float* g, float* buf, long n, float lr, flo
   return (int)hipGetLastError();
 }
 
+// slab_reduce_sgd_kernel's parameter list from the tail's logical arguments
+static void tail_launch(int blocks, void* stream, const float* P, const SlabRows& sr, int n, int stride, float* gout,
+                        float* p, float* buf, const SgdHyper& hy, int* step_counter, float* p2, const float* g2,
+                        float* buf2, int n2, int red_blocks, const TailW1& tw) {
+  TailArgs ta{};
+  ta.n = n; ta.stride = stride; ta.sr = sr; ta.p = p; ta.buf = buf;
+  ta.dlog = tw.dlog; ta.h = tw.h; ta.per_sample = tw.per_sample;
+  ta.p2w = tw.p2; ta.m2w = tw.m2; ta.pb2 = tw.pb2; ta.mb2 = tw.mb2;
+  ta.fc2 = tw.fc2; ta.loss_scale = tw.loss_scale; ta.hy = hy;
+  ta.w1g = tw.g; ta.g2w = tw.g2; ta.gb2 = tw.gb2; ta.stats = tw.stats; ta.gout = gout;
+  ta.step_counter = step_counter; ta.p2 = p2; ta.g2 = g2; ta.buf2 = buf2; ta.n2 = n2;
+  hipLaunchKernelGGL(slab_reduce_sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tw.dh, tw.a2, tw.p,
+                     tw.m, P, tw.blocks, red_blocks, tw.B, tw.grad_only, ta, dbg_next());
+}
+
 int pto_slab_reduce_sgd(const float* P, int B, int n, int stride, float* gout, float* p,
                         float* buf, float lr, float momentum, float dampening, float wd,
                         float grad_scale, int nesterov, int first_step, int* step_counter,
@@ -2768,8 +2866,7 @@ int pto_slab_reduce_sgd(const float* P, int B, int n, int stride, float* gout, f
   const int blocks = red_blocks + (n2 / 4 + 255) / 256;
   const SgdHyper hy{lr, momentum, dampening, wd, grad_scale, nesterov, first_step};
   const TailW1 tw{};
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P,
-                     sr, n, stride, gout, p, buf, hy, step_counter, p2, g2, buf2, n2, red_blocks, tw, dbg_next());
+  tail_launch(blocks, stream, P, sr, n, stride, gout, p, buf, hy, step_counter, p2, g2, buf2, n2, red_blocks, tw);
   return (int)hipGetLastError();
 }
 
@@ -2798,8 +2895,7 @@ int pto_slab_reduce_sgd_w1(const float* P, int B, int n, int stride, float* gout
   const SgdHyper hy{lr, momentum, dampening, wd, grad_scale, nesterov, first_step};
   TailW1 tw{};
   tw.dh = dh; tw.a2 = a2; tw.p = w1p; tw.m = w1m; tw.g = w1g; tw.B = B; tw.blocks = T_W1_BLOCKS;
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P,
-                     sr, n, stride, gout, p, buf, hy, step_counter, p2, g2, buf2, n2, red_blocks, tw, dbg_next());
+  tail_launch(blocks, stream, P, sr, n, stride, gout, p, buf, hy, step_counter, p2, g2, buf2, n2, red_blocks, tw);
   return (int)hipGetLastError();
 }
 
@@ -2830,9 +2926,8 @@ int pto_mnist_tail(const float* P, int B, int n, int stride, float* gout, float*
   tw.dh = dh; tw.a2 = a2; tw.p = w1p; tw.m = w1m; tw.g = w1g; tw.B = B; tw.blocks = T_W1_BLOCKS + T_FC2_BLOCKS;
   tw.fc2 = 1; tw.dlog = dlog; tw.h = h; tw.per_sample = per_sample; tw.stats = stats; tw.loss_scale = loss_scale;
   tw.p2 = p2w; tw.m2 = m2w; tw.g2 = g2w; tw.pb2 = pb2; tw.mb2 = mb2; tw.gb2 = gb2;
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P,
-                     sr, n, stride, gout, p, buf, hy, step_counter, nullptr, nullptr, nullptr, 0, red_blocks, tw,
-                     dbg_next());
+  tail_launch(blocks, stream, P, sr, n, stride, gout, p, buf, hy, step_counter, nullptr, nullptr, nullptr, 0,
+              red_blocks, tw);
   return (int)hipGetLastError();
 }
 
@@ -2859,9 +2954,8 @@ int pto_mnist_tail_grads(const float* P, int B, int n, int stride, float* gout, 
   tw.dh = dh; tw.a2 = a2; tw.g = w1g; tw.B = B; tw.blocks = T_W1_BLOCKS + T_FC2_BLOCKS;
   tw.fc2 = 1; tw.dlog = dlog; tw.h = h; tw.per_sample = per_sample; tw.stats = stats; tw.loss_scale = loss_scale;
   tw.g2 = g2w; tw.gb2 = gb2; tw.grad_only = 1;
-  hipLaunchKernelGGL(slab_reduce_sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P,
-                     sr, n, stride, gout, nullptr, nullptr, hy, nullptr, nullptr, nullptr, nullptr, 0, red_blocks, tw,
-                     dbg_next());
+  tail_launch(blocks, stream, P, sr, n, stride, gout, nullptr, nullptr, hy, nullptr, nullptr, nullptr, nullptr, 0,
+              red_blocks, tw);
   return (int)hipGetLastError();
 }
 
@@ -2881,10 +2975,7 @@ int pto_mnist_fc1_bwd_head(const float* hp0, const float* hp1, const float* w2, 
     return -1;
   if ((((uintptr_t)hp0) | ((uintptr_t)hp1) | ((uintptr_t)w2) | ((uintptr_t)h_out) | ((uintptr_t)dh_out)) & 15)
     return -2;  // float4 rows
-  Fc1BwdHead a{};
-  a.hp0 = hp0; a.hp1 = hp1; a.w2 = w2; a.b2 = b2; a.lab = lab; a.a2 = a2; a.idx2 = idx2; a.w1 = w1;
-  a.dz2 = dz2; a.dpool = dpool; a.h_out = h_out; a.dh_out = dh_out; a.dlog_out = dlog_out; a.per_sample = per_sample;
-  a.grad_scale = grad_scale; a.B = B;
+  Fc1BwdStage a{};
   int nst = 0;
   if (stage_x != nullptr) {
     if (nperm == nullptr || ncursor == nullptr || nlabels == nullptr || stage_lab == nullptr || stage_tag == nullptr ||
@@ -2898,7 +2989,8 @@ int pto_mnist_fc1_bwd_head(const float* hp0, const float* hp1, const float* w2, 
     nst = (B + 3) / 4;
   }
   const int blocks = ((B + 15) / 16) * 50 + nst;
-  hipLaunchKernelGGL(fc1_bwd_head_kernel, dim3(blocks), dim3(E_NT), 0, (hipStream_t)stream, a, dbg_next());
+  hipLaunchKernelGGL(fc1_bwd_head_kernel, dim3(blocks), dim3(E_NT), 0, (hipStream_t)stream, hp0, hp1, w2, w1, a2,
+                     dbg_next(), B, grad_scale, idx2, lab, b2, h_out, dpool, dz2, dh_out, dlog_out, per_sample, a);
   return (int)hipGetLastError();
 }
 
@@ -2924,7 +3016,7 @@ int pto_mnist_conv_bwd4(const float* dpool, const uint8_t* idx2, const float* w2
   if (rc != 0) return rc;
   const int nb = 4 * ((B + 3) / 4);
   hipLaunchKernelGGL(conv_bwd4_kernel, dim3(4, nb), dim3(F_NT), G_LDS * sizeof(float), (hipStream_t)stream,
-                     dpool, idx2, w2, a1, idx1, xn, slab, stride, o_gw2, o_gb2, o_gw1, o_gb1, B, dbg_next());
+                     dpool, idx2, w2, a1, idx1, xn, B, stride, slab, o_gw2, o_gb2, o_gw1, o_gb1, dbg_next());
   return (int)hipGetLastError();
 }
 

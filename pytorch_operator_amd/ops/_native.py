@@ -52,7 +52,12 @@ def _sources():
 # own asm MFMAs, so the compiler's MFMAs (S, dP) write VGPRs that the VALU reads directly), and
 # no SLP vectorisation: packed f32 VALU beside MFMAs costs more issue time than two scalar ops
 # (MI355X_MICROARCH.md, constants table).
-_FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+# mnist_kernels.hip: kernel-argument preloading -- the command processor writes the leading 14
+# argument dwords into user SGPRs at wave launch, so the step kernels (whose parameter lists lead
+# with what their first loads need) start without a scalar-load round trip; firmware without the
+# feature runs the compiler's compatibility prologue, which loads the same dwords.
+_FILE_FLAGS = {"mnist_kernels.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
+               "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
 
 

@@ -21,9 +21,10 @@ for f in csrc/kernels/*.hip csrc/kernels/experiments/*.hip; do
   [ "$n" = attention_bwd_pipe ] && extra="-mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize"
   [ $OBJ/$n.o -nt $f ] && [ $OBJ/$n.o -nt csrc/kernels/attention_common.h ] || { $HIPCC $FLAGS $extra -c $f -o $OBJ/$n.o & pids+=($!); }
 done
+# mnist_kernels.hip: kernel-argument preloading, as ops/_native.py (MNIST_FLAGS="" builds without)
 while [ $# -ge 2 ]; do
   name=$1; defs=$2; shift 2
-  ( $HIPCC $FLAGS $defs -c csrc/kernels/mnist_kernels.hip -o $OBJ/mnist_$name.o ) & pids+=($!)
+  ( $HIPCC $FLAGS ${MNIST_FLAGS--mllvm -amdgpu-kernarg-preload-count=16} $defs -c csrc/kernels/mnist_kernels.hip -o $OBJ/mnist_$name.o ) & pids+=($!)
   names+=($name)
 done
 for p in "${pids[@]}"; do wait $p; done

@@ -77,6 +77,48 @@ def kernel_resources(lib: Path, arch: str = "gfx950") -> dict:
     return out
 
 
+def _elf_symbols(elf: bytes):
+    """(name, value, size, section index) of every symbol of a little-endian ELF64 image, and its
+    section table [(addr, file offset, size)]."""
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+    secs = []
+    for i in range(shnum):
+        _, typ, _, addr, off, size, link, _, _, entsize = struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize)
+        secs.append((typ, addr, off, size, link, entsize))
+    syms = []
+    for typ, _, off, size, link, entsize in secs:
+        if typ not in (2, 11) or not entsize:  # SHT_SYMTAB, SHT_DYNSYM
+            continue
+        stroff = secs[link][2]
+        for j in range(size // entsize):
+            name, _, _, shndx, value, ssize = struct.unpack_from("<IBBHQQ", elf, off + j * entsize)
+            end = elf.index(b"\0", stroff + name)
+            syms.append((elf[stroff + name:end].decode(), value, ssize, shndx))
+    return syms, [(s[1], s[2], s[3]) for s in secs]
+
+
+def kernel_descriptors(lib: Path, arch: str = "gfx950") -> dict:
+    """{kernel name: {kernarg_preload_length, kernarg_preload_offset, kernarg_size}} from the
+    64-byte kernel descriptors (the ``<name>.kd`` objects) of every code object.  LLVM AMDGPU
+    kernel-descriptor layout: KERNARG_SIZE is the dword at byte 8; KERNARG_PRELOAD is the 16-bit
+    field at byte 58 -- bits 0-6 the number of SGPRs (argument dwords) the command processor
+    preloads, bits 7-15 the dword offset it starts from (checked against the
+    ``.amdhsa_user_sgpr_kernarg_preload_length`` lines of ``hipcc -S`` for mnist_kernels.hip)."""
+    out = {}
+    for _, b in ((t, b) for t, b in code_objects(lib) if arch in t):
+        syms, secs = _elf_symbols(b)
+        for name, value, size, shndx in syms:
+            if not name.endswith(".kd") or size != 64 or shndx == 0 or shndx >= len(secs):
+                continue
+            addr, off, _ = secs[shndx]
+            kd = b[off + value - addr:off + value - addr + 64]
+            preload, = struct.unpack_from("<H", kd, 58)
+            out[name[:-3]] = {"kernarg_preload_length": preload & 0x7F, "kernarg_preload_offset": preload >> 7,
+                              "kernarg_size": struct.unpack_from("<I", kd, 8)[0]}
+    return out
+
+
 def vgpr_alloc(res: dict) -> int:
     """VGPRs one wave of the kernel takes from its SIMD's 512 (arch VGPRs 4-aligned, then the
     AGPRs, in granules of 8)."""
