@@ -18,7 +18,13 @@ typedef uint16_t bf16_t;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int D = 128;       // head dim (the 8B / 70B Llama-3 value)
+// Head dim of this translation unit: 128 (the 8B / 70B Llama-3 value) unless the file defines
+// PTO_ATTN_D before including this header (attention_d64.hip: 64, the Llama-3.2 1B value).
+#ifndef PTO_ATTN_D
+#define PTO_ATTN_D 128
+#endif
+constexpr int D = PTO_ATTN_D;
+static_assert(D == 64 || D == 128, "the LDS image below is worked out for 128- and 256-byte rows");
 constexpr int NDS = D / 16;  // k-steps of a d-contraction
 constexpr int NDT = D / 32;  // 32-wide output tiles along d
 constexpr int BM = 128;      // query rows per forward / dQ workgroup (32 per wave)
@@ -26,7 +32,7 @@ constexpr int BN = 64;       // keys per K/V tile
 constexpr int BK = 128;      // keys per dK/dV workgroup (32 per wave)
 constexpr int QT = 32;       // query rows per dK/dV tile
 constexpr int NT = 256;
-constexpr int CH = D / 8;    // 16-byte chunks per row (16)
+constexpr int CH = D / 8;    // 16-byte chunks per row (16, or 8 at D = 64)
 constexpr int NT8 = 512;     // 8-wave workgroups (two waves per SIMD)
 constexpr int BM8 = 256;     // query rows per 8-wave forward / dQ workgroup
 constexpr float DEFER = 8.f; // deferred-rescale threshold of the 8-wave forward (log2 units)
@@ -35,10 +41,42 @@ __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-// XOR-swizzled image of a [rows][128] bf16 tile, in 16-byte units: chunk ch of row r.
-// Row reads of 16 consecutive rows at one chunk and transposed 4-row x 16-column reads both
-// hit 64 distinct banks.
-__device__ __forceinline__ int xo(int r, int ch) { return r * CH + (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))); }
+// XOR-swizzled image of a [rows][D] bf16 tile, in 16-byte units: chunk ch of row r sits in slot
+// ch ^ swz(r) of its own row.  bank = (byte address / 4) % 64, so the 16-byte slot s of row r
+// covers the four banks of bank-line slot (r * CH + s) % 16.
+// D = 128 (256-byte rows, one row per bank line): bank-line slot = ch ^ swz(r).
+//   Row reads (ds_read_b128, row_frag: row = lane & 31 at one chunk; each of the instruction's
+//   16-lane groups holds 16 rows distinct mod 16): swz is a bijection of r & 15, 16 distinct slots.
+//   Transposed reads (ds_read_b64_tr_b16, tr_frag: a 32-lane half takes rows 4a + q, q = 0..3, times
+//   the four chunks c0 + j of 32 columns, both 8-byte halves of each): slot = (c0 ^ 4q) + (j ^ (a & 3)),
+//   16 distinct slots, 64 distinct banks.
+// D = 64 (128-byte rows, rows 2n and 2n + 1 share a bank line): bank-line slot = 8 (r & 1) + (ch ^ swz(r)),
+//   swz(r) = 4 bit1(r) + bits 3..2 of r, a number below CH = 8.
+//   Row reads: over 16 rows distinct mod 16, r & 1 picks the half line and swz runs through all 8
+//   values once per parity (it is a bit permutation of (r >> 1) & 7): 16 distinct slots.
+//   Transposed reads: rows 4a + q, chunks c0 + j (c0 = 0 or 4): slot bit 3 = bit0(q), bit 2 =
+//   bit2(c0) ^ bit1(q), bits 1..0 = j ^ (a & 3): 16 distinct slots, 64 distinct banks.
+//   The plain XOR of D = 128 would leave the row at CH = 8 (its values reach 15).
+// Both: a Stage / rows_from_lds group of 16 lanes covers whole rows (one at D = 128, two
+// adjacent ones at D = 64), i.e. one whole bank line.
+constexpr int swz(int r) {
+  return D == 128 ? (((r & 3) << 2) | ((r >> 2) & 3)) : ((((r >> 1) & 1) << 2) | ((r >> 2) & 3));
+}
+constexpr int xo(int r, int ch) { return r * CH + (ch ^ swz(r)); }
+
+// A wrong swizzle must fail the build, not corrupt a neighbouring row: over a tile of `rows` rows
+// every (row, chunk) lands inside the tile, inside its own row, and no two collide.
+constexpr bool xo_permutes(int rows) {
+  bool seen[BM * CH] = {};
+  for (int r = 0; r < rows; ++r)
+    for (int ch = 0; ch < CH; ++ch) {
+      const int o = xo(r, ch);
+      if (o < 0 || o >= rows * CH || o / CH != r || seen[o]) return false;
+      seen[o] = true;
+    }
+  return true;
+}
+static_assert(xo_permutes(QT) && xo_permutes(BN) && xo_permutes(BM), "xo() must permute each row's chunks");
 
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
   uint32_t r;
@@ -113,8 +151,8 @@ __device__ __forceinline__ float bf2f(uint16_t u) { return __uint_as_float((uint
 // a value every lane of the wave holds, moved to a scalar register
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
-// Stage a [ROWS][128] bf16 tile (rows ROWS apart in global by `stride` elements) into the
-// XOR image: each thread moves ROWS*16/NT 16-byte chunks.
+// Stage a [ROWS][D] bf16 tile (rows ROWS apart in global by `stride` elements) into the
+// XOR image: each thread moves ROWS*CH/NT 16-byte chunks.
 template <int ROWS, int NTH = NT>
 struct Stage {
   static constexpr int N = ROWS * CH / NTH;
@@ -148,7 +186,7 @@ __device__ __forceinline__ void glds_tile(const bf16_t* base, size_t stride, u32
   for (int i = 0; i < NP / NW; ++i) {
     const int p = w + NW * i;
     const int e = 64 * p + lane, row = e / CH, j = e % CH;
-    const int ch = j ^ (((row & 3) << 2) | ((row >> 2) & 3));
+    const int ch = j ^ swz(row);
     __builtin_amdgcn_global_load_lds(base + (size_t)row * stride + ch * 8,
                                      (__attribute__((address_space(3))) void*)(tile + 64 * p), 16, 0, 0);
   }
@@ -168,7 +206,7 @@ __device__ __forceinline__ void glds_tile_asm(const bf16_t* base, size_t stride,
   for (int i = 0; i < NP / NW; ++i) {
     const int p = w + NW * i;
     const int e = 64 * p + lane, row = e / CH, j = e % CH;
-    const int ch = j ^ (((row & 3) << 2) | ((row >> 2) & 3));
+    const int ch = j ^ swz(row);
     const bf16_t* src = base + (size_t)row * stride + ch * 8;
     const unsigned dst = (unsigned)(uintptr_t)(tile + 64 * p);  // LDS byte address, wave-uniform
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
@@ -181,8 +219,8 @@ __device__ __forceinline__ void glds_dword_asm(const float* src, float* lds_dst)
                :: "s"(__builtin_amdgcn_readfirstlane(dst)), "v"(src) : "memory", "m0");
 }
 
-// Write a wave's 32 x 128 transposed accumulator (acc[dt] reg i = [d = dt*32 + acc_row(i,h)]
-// [col = lane & 31]) as rows [col][d] bf16 to global via the wave's LDS region (8 KB): the two
+// Write a wave's 32 x D transposed accumulator (acc[dt] reg i = [d = dt*32 + acc_row(i,h)]
+// [col = lane & 31]) as rows [col][d] bf16 to global via the wave's LDS region (32 rows): the two
 // halves, then the two forms of the hand-off between them.
 __device__ __forceinline__ void rows_T_to_lds(const f32x16 (&acc)[NDT], float scale, u32x4* stage, int lane) {
   const int c = lane & 31, h = lane >> 5;

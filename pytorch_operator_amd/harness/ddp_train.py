@@ -26,7 +26,7 @@ import os
 import sys
 import time
 
-MODELS = ("resnet50", "resnet-tiny", "llama3-8b", "llama3-1b", "llama-tiny", "llama-mini")
+MODELS = ("resnet50", "resnet-tiny", "llama3-8b", "llama3-1b", "llama-tiny", "llama-mini", "llama-mini64")
 
 
 def parse_args(argv=None):

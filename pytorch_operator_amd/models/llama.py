@@ -11,7 +11,7 @@ GQA attention with RoPE (theta 500 000) -> residual, RMSNorm -> SwiGLU FFN -> re
 final RMSNorm, untied output projection.  Matmuls run in bf16 under autocast
 (hipBLASLt); attention runs the hand-written HIP flash attention (``ops.attention``, forward
 and backward on MFMA, token-major [B, S, H, D] in and out, so no transposes around it) for
-bf16 head_dim-128 shapes and ``scaled_dot_product_attention`` otherwise (``impl`` = "sdpa"
+bf16 head_dim-128 and head_dim-64 shapes and ``scaled_dot_product_attention`` otherwise (``impl`` = "sdpa"
 forces the library path for A/B runs).
 The elementwise work between the matmuls runs as hand-written HIP kernels on a GPU:
 RMSNorm (``ops.norm``, fp32 statistics over the fp32 residual stream, bf16 output under
@@ -60,6 +60,9 @@ CONFIGS = {
     # smallest config with the 8B model's head_dim (128): exercises the HIP flash attention
     "llama-mini": LlamaConfig(dim=512, n_layers=2, n_heads=4, n_kv_heads=2, vocab_size=512, ffn_hidden=1024,
                               max_seq_len=1024),
+    # the same at the 1B model's head_dim (64)
+    "llama-mini64": LlamaConfig(dim=256, n_layers=2, n_heads=4, n_kv_heads=2, vocab_size=512, ffn_hidden=512,
+                                max_seq_len=1024),
 }
 
 

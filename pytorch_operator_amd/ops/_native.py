@@ -48,6 +48,7 @@ def _sources():
 # accumulators the compiler moved them between AGPRs and VGPRs every tile (298 v_accvgpr_read +
 # 261 v_accvgpr_write in the kernel against 31 + 22 with VGPR form).  Its document-masked kernels
 # are in the same file as the plain 4-wave ones they derive from, so they are built with the same flags.
+# attention_d64.hip: the same 4-wave kernel text (attention_4wave.h) at head dim 64, same flags.
 # attention_bwd_pipe.hip: VGPR form as well (its dK/dV accumulators are pinned in AGPRs by its
 # own asm MFMAs, so the compiler's MFMAs (S, dP) write VGPRs that the VALU reads directly), and
 # no SLP vectorisation: packed f32 VALU beside MFMAs costs more issue time than two scalar ops
@@ -58,6 +59,7 @@ def _sources():
 # feature runs the compiler's compatibility prologue, which loads the same dwords.
 _FILE_FLAGS = {"mnist_kernels.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
                "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "attention_d64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
 
 

@@ -1,12 +1,14 @@
-"""Flash attention (``csrc/kernels/attention.hip``) as an autograd op for the Llama worker.
+"""Flash attention (``csrc/kernels/attention.hip``, ``attention_d64.hip``) as an autograd op for the
+Llama worker.
 
 ``flash_attention(q, k, v, causal=True)``: q [B, S, Hq, D], k/v [B, S, Hkv, D] (GQA when
 Hkv < Hq), token-major like the projections that produce them, so no transposes or copies
 surround the kernels; returns o [B, S, Hq, D] (``o.reshape(B, S, Hq * D)`` feeds the output
 projection).  Scale 1/sqrt(D).
 
-The HIP path covers the Llama-3 attention shapes: bf16, D = 128, S a multiple of 128
-(``hip_supported``).  The forward keeps lse2 = log2-sum-exp of the scaled scores per query
+The HIP path covers the Llama-3 attention shapes: bf16, D = 128 (8B / 70B) or 64 (Llama-3.2 1B),
+S a multiple of 128 (``hip_supported``).  D = 64 runs the 4-wave kernels only: the 8-wave forward,
+the pipelined backward and the variant setters are D = 128.  The forward keeps lse2 = log2-sum-exp of the scaled scores per query
 row; the backward is two launches (dQ with delta = rowsum(dO * O), then dK/dV), both
 deterministic.  On CPU the same math runs in PyTorch (``attention_reference``); a GPU call
 with an unsupported shape raises instead of falling back silently.
@@ -28,7 +30,8 @@ import torch.nn.functional as F
 
 from . import _native
 
-HEAD_DIM = 128
+HEAD_DIM = 128         # the 8B model's
+HEAD_DIMS = (64, 128)  # every head dim the HIP kernels are built for
 SEQ_MULTIPLE = 128
 
 
@@ -45,7 +48,7 @@ def hip_supported(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> bool:
     if not (q.is_cuda and k.is_cuda and v.is_cuda) or q.dim() != 4:
         return False
     B, S, Hq, D = q.shape
-    return (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D == HEAD_DIM and S % SEQ_MULTIPLE == 0
+    return (q.dtype == k.dtype == v.dtype == torch.bfloat16 and D in HEAD_DIMS and S % SEQ_MULTIPLE == 0
             and k.shape == v.shape and k.shape[0] == B and k.shape[1] == S and k.shape[3] == D
             and Hq % k.shape[2] == 0)
 
@@ -206,7 +209,7 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     if not q.is_cuda:
         return attention_reference(q, k, v, causal, doc_start=doc_start)
     if not hip_supported(q, k, v):
-        raise ValueError(f"flash_attention: HIP path needs bf16 [B,S,H,{HEAD_DIM}] with S % {SEQ_MULTIPLE} == 0 "
+        raise ValueError(f"flash_attention: HIP path needs bf16 [B,S,H,D] with D in {HEAD_DIMS}, S % {SEQ_MULTIPLE} == 0 "
                          f"and Hq % Hkv == 0; got q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)}")
     if doc_start is not None:
         return _FlashAttentionDoc.apply(_c(q), _c(k), _c(v), *_doc_bounds(doc_start))

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Attention kernel timing at Llama-3 8B shapes: HIP flash attention vs the library SDPA.
+"""Attention kernel timing at Llama-3 shapes: HIP flash attention vs the library SDPA.
 
-usage: python tools/attn_bench.py [--batch 4] [--seq 2048] [--hq 32] [--hkv 8] [--reps 20] [--json-out F]
-                                  [--doc-len-mean N]
+usage: python tools/attn_bench.py [--batch 4] [--seq 2048] [--hq 32] [--hkv 8] [--head-dim 128] [--reps 20]
+                                  [--json-out F] [--doc-len-mean N]
+
+--head-dim 64 is the Llama-3.2 1B shape (the 4-wave kernels of attention_d64.hip).
 
 Times forward alone and forward+backward (CUDA events, median of reps); FLOPs count the
 causal half: fwd 2 products, bwd 5 products (the HIP backward does 7: see attention.hip).
@@ -62,6 +64,7 @@ def main():
     p.add_argument("--seq", type=int, default=2048)
     p.add_argument("--hq", type=int, default=32)
     p.add_argument("--hkv", type=int, default=8)
+    p.add_argument("--head-dim", type=int, default=128)
     p.add_argument("--reps", type=int, default=20)
     p.add_argument("--causal", type=int, default=1)
     p.add_argument("--impl", default="hip,sdpa")
@@ -69,7 +72,7 @@ def main():
     p.add_argument("--json-out", default=None)
     a = p.parse_args()
     from pytorch_operator_amd.ops.attention import flash_attention, sdpa_bshd, validate_doc_start
-    B, S, Hq, Hkv, D = a.batch, a.seq, a.hq, a.hkv, 128
+    B, S, Hq, Hkv, D = a.batch, a.seq, a.hq, a.hkv, a.head_dim
     g = torch.Generator(device="cuda").manual_seed(0)
     q = torch.randn(B, S, Hq, D, device="cuda", generator=g).to(torch.bfloat16).requires_grad_(True)
     k = torch.randn(B, S, Hkv, D, device="cuda", generator=g).to(torch.bfloat16).requires_grad_(True)

@@ -18,6 +18,7 @@ pids=()
 for f in csrc/kernels/*.hip; do
   n=$(basename $f .hip); [ "$n" = attention_bwd_pipe ] && continue
   extra=""; [ "$n" = attention ] && extra="-mllvm -amdgpu-mfma-vgpr-form=1"
+  [ "$n" = attention_d64 ] && extra="-mllvm -amdgpu-mfma-vgpr-form=1"
   [ $OBJ/$n.o -nt $f ] && [ $OBJ/$n.o -nt csrc/kernels/attention_common.h ] || { $HIPCC $FLAGS $extra -c $f -o $OBJ/$n.o & pids+=($!); }
 done
 names=()

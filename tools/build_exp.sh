@@ -18,6 +18,7 @@ for f in csrc/kernels/*.hip csrc/kernels/experiments/*.hip; do
   n=$(basename $f .hip); [ "$n" = mnist_kernels ] && continue
   extra=""; [ "$n" = attention ] && extra="${ATTN_FLAGS--mllvm -amdgpu-mfma-vgpr-form=1}"  # as ops/_native.py
   [ "$n" = attention_variants ] && extra="-mllvm -amdgpu-mfma-vgpr-form=1"
+  [ "$n" = attention_d64 ] && extra="-mllvm -amdgpu-mfma-vgpr-form=1"
   [ "$n" = attention_bwd_pipe ] && extra="-mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize"
   [ $OBJ/$n.o -nt $f ] && [ $OBJ/$n.o -nt csrc/kernels/attention_common.h ] || { $HIPCC $FLAGS $extra -c $f -o $OBJ/$n.o & pids+=($!); }
 done
