@@ -117,6 +117,10 @@ def parse_args(argv=None):
                    help="Llama: micro-batches of --batch-size sequences per optimizer step.  Master-weight / "
                         "ZeRO: their gradients are summed in fp32 accumulators (csrc/kernels/gradaccum.hip) and "
                         "reduced once per step; data parallelism needs --zero 1")
+    p.add_argument("--opt-state", choices=["fp32", "bf16"], default="fp32",
+                   help="Llama, master-weight / ZeRO: dtype of the AdamW moments.  bf16 halves them (4 B per "
+                        "parameter instead of 8) and the update pass rounds them stochastically, seeded by --seed "
+                        "(csrc/kernels/adamw.hip); the master weights stay fp32")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
@@ -127,6 +131,10 @@ def parse_args(argv=None):
         p.error("--grad-accum: a positive number of micro-batches")
     if args.grad_accum > 1 and not args.model.startswith("llama"):
         p.error("--grad-accum is for the Llama models")
+    if args.opt_state != "fp32" and (not args.model.startswith("llama") or args.dtype != "bf16"
+                                     or args.master_weights == "off"):
+        p.error("--opt-state bf16 is for the master-weight / ZeRO AdamW: a Llama model with --dtype bf16 and "
+                "master weights")
     return args
 
 
@@ -172,6 +180,9 @@ def build(args, device, world: int = 1):
         model = Llama(CONFIGS[args.model], checkpoint_layers=args.grad_checkpoint)
     clip = {"max_grad_norm": args.max_grad_norm} if args.max_grad_norm > 0 else {}
     accum = {"grad_accum": args.grad_accum} if args.grad_accum > 1 else {}
+    state = {"state_dtype": torch.bfloat16, "state_seed": args.seed} if args.opt_state == "bf16" else {}
+    if state and not (use_zero(args, device, world) or use_master_weights(args, device)):
+        raise SystemExit("error: --opt-state bf16 needs the master-weight optimizer (--master-weights on, or a GPU)")
     if use_zero(args, device, world):
         from ..ops.optim import to_bf16_matmul_weights
         from ..parallel.zero import ZeroAdamW
@@ -182,14 +193,14 @@ def build(args, device, world: int = 1):
         opt = ZeroAdamW(model, lr=args.lr or 3e-4, betas=(0.9, 0.95), weight_decay=0.1,
                         bucket_mb=args.zero_bucket_mb,
                         reduce_dtype=torch.bfloat16 if args.allreduce_dtype == "bf16" else torch.float32,
-                        grad_view=bool(args.zero_grad_view), **clip, **accum)
+                        grad_view=bool(args.zero_grad_view), **clip, **accum, **state)
         return model, opt
     if use_master_weights(args, device):
         from ..ops.optim import MasterAdamW, install_overlap, to_bf16_matmul_weights
         to_bf16_matmul_weights(model)
         overlap = args.opt_overlap == "on" and device.type == "cuda"
         opt = MasterAdamW(model.parameters(), lr=args.lr or 3e-4, betas=(0.9, 0.95), weight_decay=0.1,
-                          overlap=overlap, **clip, **accum)
+                          overlap=overlap, **clip, **accum, **state)
         if overlap:
             install_overlap(model)
         return model, opt
@@ -252,6 +263,15 @@ def use_master_weights(args, device) -> bool:
     if not args.model.startswith("llama") or args.dtype != "bf16":
         return False
     return args.master_weights == "on" or (args.master_weights == "auto" and device.type == "cuda")
+
+
+def optimizer_state_bytes(opt) -> int:
+    """Bytes of optimizer state this rank holds: fp32 masters + both moments (``ZeroAdamW``: of its
+    shards; ``MasterAdamW``: of every parameter that has stepped)."""
+    if hasattr(opt, "state_bytes"):
+        return opt.state_bytes()
+    return sum(t.numel() * t.element_size() for st in opt.state.values()
+               for t in (st.get("master"), st.get("exp_avg"), st.get("exp_avg_sq")) if t is not None)
 
 
 def fp32_allreduce_hook(process_group, bucket):
@@ -494,6 +514,8 @@ def main(argv=None) -> int:
         res.update(linear_dtype=args.linear_dtype, grad_format=args.fp8_grad_format)
     if N > 1:
         res.update(grad_accum=N)
+    if res["master_weights"]:
+        res.update(opt_state=args.opt_state, optimizer_state_bytes=optimizer_state_bytes(opt))
     if is_llama and doc_start is not None:
         res.update(doc_len_mean=args.doc_len_mean, docs_per_seq=round(docs_per_seq, 2), attn_mask="document")
     if tuning.get("mode") == "tune" and rank == 0:

@@ -197,6 +197,10 @@ _SIGNATURES = {
     # adamw.hip
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
     "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
+    "pto_adamw_bf16state_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F,
+                                   ctypes.c_uint32, ctypes.c_uint64, _VP],
+    "pto_adamw_bf16state_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F,
+                                    ctypes.c_uint32, ctypes.c_uint64, _VP],
     # gradclip.hip
     "pto_grad_sumsq": [_VP, _L, _I, _F, _VP, _L, _VP],
     "pto_grad_sumsq_finish": [_VP, _L, _VP, _VP],

@@ -6,7 +6,8 @@ and bf16->fp32 gradient casts disappear -- and ``MasterAdamW`` keeps an fp32 mas
 of those weights plus fp32 moments.  Other parameters (embedding, RMSNorm weights) stay
 fp32 and are their own master.  One fused HIP pass per parameter (``adamw_launch``) updates
 master, m, v and rewrites the bf16 weight.  Update rule = ``torch.optim.AdamW`` (decoupled
-decay, bias-corrected moments), applied to the fp32 master.
+decay, bias-corrected moments), applied to the fp32 master.  ``state_dtype=torch.bfloat16`` stores the
+moments in bf16 with stochastic rounding (``sr_key`` / ``sr_bits`` / ``sr_round_bf16`` are the rule).
 
 On CPU the same update runs in PyTorch (``MasterAdamW._step_reference``: CPU tests, gloo
 plumbing).  ``parallel/zero.py`` applies both to its bucket shards.
@@ -20,6 +21,58 @@ import torch
 import torch.nn as nn
 
 from . import _native
+
+
+_M32 = 0xFFFFFFFF
+
+
+def _mix32(x: int) -> int:
+    x &= _M32
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M32
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M32
+    x ^= x >> 16
+    return x
+
+
+def sr_key(seed: int, step: int) -> int:
+    """The 32-bit key of one AdamW pass with bf16 moments: ``mix(seed + 0x9E3779B9 * step)`` in
+    wrapping uint32 arithmetic, ``step`` the pass's step count (>= 1)."""
+    return _mix32(int(seed) + 0x9E3779B9 * int(step))
+
+
+def _mul32(x: torch.Tensor, c: int) -> torch.Tensor:
+    # x * c mod 2^32 on int64 tensors holding uint32 values, without leaving the int64 range
+    return ((x & 0xFFFF) * c + ((((x >> 16) * c) & 0xFFFF) << 16)) & _M32
+
+
+def _mix32_t(x: torch.Tensor) -> torch.Tensor:
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def sr_bits(key: int, base: int, n: int, device=None) -> torch.Tensor:
+    """The kernel's 32 random bits of elements ``base .. base + n`` (csrc/kernels/adamw.hip,
+    ``sr_bits``) as an int64 tensor: ``mix(mix(lo32(c) ^ key) + hi32(c))``."""
+    c = torch.arange(n, dtype=torch.int64, device=device)
+    lo = (c + (int(base) & _M32))          # < 2^33: the carry into the high word is bit 32
+    hi = ((int(base) >> 32) + (lo >> 32)) & _M32
+    return _mix32_t((_mix32_t((lo & _M32) ^ int(key)) + hi) & _M32)
+
+
+def sr_round_bf16(x: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """fp32 ``x`` -> bf16, rounded away from zero with probability (its low 16 bits) / 65536 given
+    ``r`` uniform in [0, 65535]: ``(bits(x) + r) >> 16``; a NaN becomes a quiet NaN of its sign.  A
+    bf16-representable value (+-0, +-inf) never changes."""
+    u = x.contiguous().view(torch.int32).to(torch.int64) & _M32
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    b = torch.where(nan, (u >> 16) | 0x40, (u + r) >> 16)
+    b = torch.where(b >= 0x8000, b - 0x10000, b)
+    return b.to(torch.int16).view(torch.bfloat16)
 
 
 def to_bf16_matmul_weights(model: nn.Module) -> int:
@@ -59,13 +112,28 @@ class MasterAdamW(torch.optim.Optimizer):
     1/N as their gradient scale.  The accumulators (4 B per parameter, kept from step to step) are
     no optimizer state: they are empty at every step boundary and stay out of ``state_dict()``.
     Under ``DistributedDataParallel`` the comm hook would reduce only the last micro-batch: data
-    parallelism with ``grad_accum > 1`` is ``ZeroAdamW``'s."""
+    parallelism with ``grad_accum > 1`` is ``ZeroAdamW``'s.
+
+    ``state_dtype=torch.bfloat16`` (default fp32: nothing below exists): ``exp_avg`` / ``exp_avg_sq``
+    are stored in bf16, 4 B per parameter instead of 8, and the update pass moves 20 B per
+    bf16-weight element instead of 28.  Each pass widens them, updates the fp32 master from the fp32
+    moments, and rounds the moments stochastically (round-to-nearest would freeze ``v``: its decay of
+    ``1 - b2`` per step is below half a bf16 ulp).  The random bits are a hash of (``state_seed``,
+    the parameter's step count, the element's index among all parameters in ``param_groups`` order),
+    so a run is reproducible and a resumed one continues bit for bit.  ``ZeroAdamW`` counts elements
+    by bucket, so the two optimizers do not agree bit for bit at bf16 state (they do at fp32); nor
+    do the CPU and GPU paths."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, overlap=False,
-                 max_grad_norm=None, grad_accum=1):
+                 max_grad_norm=None, grad_accum=1, state_dtype=torch.float32, state_seed=0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if int(grad_accum) != grad_accum or grad_accum < 1:
             raise ValueError("grad_accum: a positive integer")
+        if state_dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("state_dtype: float32 or bfloat16")
+        self.state_dtype = state_dtype
+        self.state_seed = int(state_seed)
+        self._base = None  # bf16 state: parameter -> index of its first element among all parameters
         self.grad_accum = int(grad_accum)
         self._micro = 0   # accumulate() calls since the last step()
         self._acc = {}    # grad_accum > 1: parameter -> its fp32 accumulator
@@ -96,9 +164,24 @@ class MasterAdamW(torch.optim.Optimizer):
                     del p._pto_master
             else:
                 st["master"] = None
-            st["exp_avg"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
-            st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.zeros(p.shape, dtype=self.state_dtype, device=p.device)
+            st["exp_avg_sq"] = torch.zeros(p.shape, dtype=self.state_dtype, device=p.device)
         return st
+
+    def _rng(self, p, step):
+        """bf16 moments: (key, base) of parameter ``p``'s pass at its step count ``step``.  The bases
+        follow ``param_groups`` order and are not checkpointed: a resumed run continues bit for bit
+        only if it builds the optimizer with the same parameters in the same order (a group added
+        later appends, and leaves the earlier bases alone)."""
+        if self.state_dtype == torch.float32:
+            return None
+        if self._base is None or p not in self._base:
+            self._base, off = {}, 0
+            for group in self.param_groups:
+                for q in group["params"]:
+                    self._base[q] = off
+                    off += q.numel()
+        return sr_key(self.state_seed, step), self._base[p]
 
     @torch.no_grad()
     def accumulate(self):
@@ -201,12 +284,13 @@ class MasterAdamW(torch.optim.Optimizer):
             st = self._state(p)
             st["step"] += 1
             master = st["master"] if st["master"] is not None else p
+            rng = self._rng(p, st["step"])
             if p.is_cuda:
                 if clip is None:
                     g = self._hip_grad(p, g)  # a fix-up copy lives until this launch only
                 adamw_launch(master, st["exp_avg"], st["exp_avg_sq"], g, p if master is not p else None, p.numel(),
                              st["step"], lr, b1, b2, eps, wd, scale,
-                             None if clip is None else (clip.out, clip.max_norm))
+                             None if clip is None else (clip.out, clip.max_norm), rng)
                 if side is not None:
                     ev = torch.cuda.Event()
                     ev.record(side)
@@ -214,17 +298,28 @@ class MasterAdamW(torch.optim.Optimizer):
             else:
                 if self.grad_accum > 1:
                     g = g * scale
-                self._step_reference(p, g if clip is None else g.float() * clip.coef, master, st, lr, b1, b2, eps, wd)
+                self._step_reference(p, g if clip is None else g.float() * clip.coef, master, st, lr, b1, b2, eps, wd,
+                                     rng)
 
     @staticmethod
-    def _step_reference(p, g, master, st, lr, b1, b2, eps, wd):
+    def _step_reference(p, g, master, st, lr, b1, b2, eps, wd, rng=None):
+        """``rng=(key, base)``: the moments in ``st`` are bf16 -- widened, updated in fp32 (the master
+        from the fp32 moments), and stored back rounded stochastically with the kernel's hash."""
         g = g.float()
         t = st["step"]
+        bf16_state = st["exp_avg"].dtype == torch.bfloat16
+        if bf16_state != (rng is not None):
+            raise ValueError("AdamW: rng=(key, base) goes with bf16 moments, and only with them")
+        m, v = (st["exp_avg"].float(), st["exp_avg_sq"].float()) if bf16_state else (st["exp_avg"], st["exp_avg_sq"])
         master.mul_(1 - lr * wd)
-        st["exp_avg"].lerp_(g, 1 - b1)
-        st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
-        denom = (st["exp_avg_sq"].sqrt() / math.sqrt(1 - b2 ** t)).add_(eps)
-        master.addcdiv_(st["exp_avg"], denom, value=-lr / (1 - b1 ** t))
+        m.lerp_(g, 1 - b1)
+        v.mul_(b2).addcmul_(g, g, value=1 - b2)
+        denom = (v.sqrt() / math.sqrt(1 - b2 ** t)).add_(eps)
+        master.addcdiv_(m, denom, value=-lr / (1 - b1 ** t))
+        if bf16_state:
+            h = sr_bits(rng[0], rng[1], m.numel(), m.device).view(m.shape)
+            st["exp_avg"].copy_(sr_round_bf16(m, h & 0xFFFF))
+            st["exp_avg_sq"].copy_(sr_round_bf16(v, h >> 16))
         if master is not p:
             p.copy_(master)
 
@@ -238,18 +333,33 @@ class MasterAdamW(torch.optim.Optimizer):
         return g
 
 
-def adamw_launch(master, exp_avg, exp_avg_sq, grad, out, n, step, lr, b1, b2, eps, wd, grad_scale=1.0, clip=None):
+def adamw_launch(master, exp_avg, exp_avg_sq, grad, out, n, step, lr, b1, b2, eps, wd, grad_scale=1.0, clip=None,
+                 rng=None):
     """One fused AdamW pass (``csrc/kernels/adamw.hip``) over ``n`` elements on the current stream:
     the package's only call of the ``pto_adamw_*`` entry points.  ``out``: the bf16 weight to
     refresh (``None``: ``master`` is the parameter).  ``grad_scale`` multiplies the gradient first.
     ``clip=(norm_out, max_norm)``: also clip by the global norm whose sum of squares is the device
-    float ``norm_out[0]`` (``gradclip.GlobalGradNorm``)."""
+    float ``norm_out[0]`` (``gradclip.GlobalGradNorm``).  ``rng=(key, base)``: required with bf16
+    moments (the stochastic-rounding kernels: ``key = sr_key(seed, step)``, ``base`` the counter of
+    element 0), rejected with fp32 ones."""
+    if exp_avg.dtype != exp_avg_sq.dtype or exp_avg.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("adamw_launch: both moments fp32, or both bf16")
+    bf16_state = exp_avg.dtype == torch.bfloat16
+    if bf16_state != (rng is not None):
+        raise ValueError("adamw_launch: rng=(key, base) goes with bf16 moments, and only with them")
     lib = _native.load()
     args = (master.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.data_ptr(),
             None if out is None else out.data_ptr(), n, 1 if grad.dtype == torch.bfloat16 else 0, lr, b1, b2, eps, wd,
             step, grad_scale)
     stream = ctypes.c_void_p(torch.cuda.current_stream(master.device).cuda_stream)
-    if clip is None:
+    if bf16_state:
+        key, base = int(rng[0]) & _M32, int(rng[1])
+        if clip is None:
+            _native.check(lib.pto_adamw_bf16state_scaled(*args, key, base, stream), "adamw_bf16state")
+        else:
+            _native.check(lib.pto_adamw_bf16state_clipped(*args, clip[0].data_ptr(), clip[1], key, base, stream),
+                          "adamw_bf16state_clipped")
+    elif clip is None:
         _native.check(lib.pto_adamw_step_scaled(*args, stream), "adamw_step")
     else:
         _native.check(lib.pto_adamw_step_clipped(*args, clip[0].data_ptr(), clip[1], stream), "adamw_step_clipped")

@@ -42,7 +42,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ..ops.optim import MasterAdamW, adamw_launch
+from ..ops.optim import MasterAdamW, adamw_launch, sr_key
 
 _ALIGN = 64  # shard lengths are multiples of this (16-byte aligned fp32 / bf16 shard pointers)
 
@@ -66,8 +66,9 @@ class _Sink:
 
 class _Bucket:
     def __init__(self, params: List[nn.Parameter], world: int, rank: int, reduce_dtype=torch.float32,
-                 accum: bool = False):
+                 accum: bool = False, state_dtype=torch.float32, rng_base: int = 0):
         self.params = params
+        self.rng_base = rng_base  # bf16 moments: elements (npad) of the buckets before this one
         self.dtype = params[0].dtype
         dev = params[0].device
         n = sum(p.numel() for p in params)
@@ -116,8 +117,8 @@ class _Bucket:
         # fp32 master of the owned shard (None: fp32 weights are their own master)
         self.master = masters[self.lo:self.lo + self.shard].clone() if masters is not None else None
         del masters
-        self.exp_avg = torch.zeros(self.shard, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(self.shard, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros(self.shard, dtype=state_dtype, device=dev)
+        self.exp_avg_sq = torch.zeros(self.shard, dtype=state_dtype, device=dev)
         self.pending = len(params)
         self.arrived: set = set()  # ids of the parameters whose gradient was deposited this step
         self.rs_work = None
@@ -176,13 +177,26 @@ class ZeroAdamW:
     staging buffer is released.  On the last micro-batch the accumulator is reduce-scattered (fp32
     reduce), or the bf16 rounding of it that the same fold wrote (bf16 reduce; in place in a bf16
     staging buffer); at world 1 the accumulator is the gradient shard.  The norm pass and AdamW
-    apply 1/(N*W) as their gradient scale."""
+    apply 1/(N*W) as their gradient scale.
+
+    ``state_dtype=torch.bfloat16`` (default fp32): the moments of every shard are bf16, rounded
+    stochastically by each AdamW pass (``MasterAdamW``'s docstring has the rule).  An element's
+    random bits are a hash of (``state_seed``, the pass's step count, its position: the ``npad`` of
+    the buckets before its own plus its offset in the bucket), so a shard's bits do not depend on
+    which launch updates it and a resumed run continues bit for bit.  The positions follow the
+    bucket layout, which changes with the world size and differs from ``MasterAdamW``'s parameter
+    order: at bf16 state the result equals neither another world size's nor ``MasterAdamW``'s bit
+    for bit (the fp32-state identities above are unaffected)."""
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  group=None, bucket_mb: float = 256.0, reduce_dtype=torch.float32, grad_view: bool = True,
-                 max_grad_norm=None, grad_accum=1):
+                 max_grad_norm=None, grad_accum=1, state_dtype=torch.float32, state_seed=0):
         if int(grad_accum) != grad_accum or grad_accum < 1:
             raise ValueError("grad_accum: a positive integer")
+        if state_dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("state_dtype: float32 or bfloat16")
+        self.state_dtype = state_dtype
+        self.state_seed = int(state_seed)
         self.grad_accum = int(grad_accum)
         self._micro = 0  # accumulate() calls since the last step()
         accum = self.grad_accum > 1
@@ -217,17 +231,22 @@ class ZeroAdamW:
         self.buckets: List[_Bucket] = []
         open_: Dict[torch.dtype, List[nn.Parameter]] = {}
         size: Dict[torch.dtype, int] = {}
+
+        def close(cur):
+            self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype, accum, state_dtype,
+                                        sum(b.npad for b in self.buckets)))
+
         for p in reversed(params):
             cur = open_.setdefault(p.dtype, [])
             if cur and size[p.dtype] + p.numel() > cap:
-                self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype, accum))
+                close(cur)
                 cur = open_[p.dtype] = []
                 size[p.dtype] = 0
             cur.append(p)
             size[p.dtype] = size.get(p.dtype, 0) + p.numel()
         for cur in open_.values():
             if cur:
-                self.buckets.append(_Bucket(cur, self.world, self.rank, reduce_dtype, accum))
+                close(cur)
         self._of: Dict[int, _Bucket] = {id(p): b for b in self.buckets for p in b.params}
         for p in params:
             p.register_post_accumulate_grad_hook(self._on_grad)
@@ -499,10 +518,13 @@ class ZeroAdamW:
         w = b.w_shard()
         master = b.master if b.master is not None else w
         clip = self._clip
+        rng = None
+        if self.state_dtype == torch.bfloat16:
+            rng = (sr_key(self.state_seed, t), b.rng_base + b.lo)
         if w.is_cuda:
             adamw_launch(master, b.exp_avg, b.exp_avg_sq, b.gshard, w if b.master is not None else None, b.shard, t,
                          self.lr, b1, b2, self.eps, self.weight_decay, self._gscale(b),
-                         None if clip is None else (clip.out, clip.max_norm))
+                         None if clip is None else (clip.out, clip.max_norm), rng)
         else:
             st = {"step": t, "exp_avg": b.exp_avg, "exp_avg_sq": b.exp_avg_sq}
             g = b.gshard
@@ -510,7 +532,7 @@ class ZeroAdamW:
                 g = g.float() * self._gscale(b)
             if clip is not None:
                 g = g.float() * clip.coef
-            MasterAdamW._step_reference(w, g, master, st, self.lr, b1, b2, self.eps, self.weight_decay)
+            MasterAdamW._step_reference(w, g, master, st, self.lr, b1, b2, self.eps, self.weight_decay, rng)
 
     def _wait_weights(self, buckets) -> None:
         for b in buckets:
@@ -527,6 +549,7 @@ class ZeroAdamW:
         """This rank's optimizer shard: step count + fp32 master / moments of each bucket's slice
         (the weights themselves are in the model's state_dict)."""
         return {"t": self.t, "world": self.world, "rank": self.rank,
+                "state_dtype": "bf16" if self.state_dtype == torch.bfloat16 else "fp32",
                 "buckets": [{"npad": b.npad, "master": b.master, "exp_avg": b.exp_avg,
                              "exp_avg_sq": b.exp_avg_sq,
                              "pstep": [self.pstep.get(id(p), self.t) for p in b.params]} for b in self.buckets]}
@@ -535,6 +558,11 @@ class ZeroAdamW:
     def load_shard_state_dict(self, sd: dict) -> None:
         if sd["world"] != self.world or sd["rank"] != self.rank or len(sd["buckets"]) != len(self.buckets):
             raise ValueError("ZeRO shard checkpoint was written by a different world / rank / bucket layout")
+        have = "bf16" if self.state_dtype == torch.bfloat16 else "fp32"
+        got = sd.get("state_dtype", "fp32")  # checkpoints from before the field hold fp32 moments
+        if got != have or any(s[k].dtype != self.state_dtype for s in sd["buckets"] for k in ("exp_avg", "exp_avg_sq")):
+            raise ValueError(f"ZeRO shard checkpoint holds {got} moments, the optimizer was built with {have} "
+                             "(state_dtype): they are never cast")
         for b, s in zip(self.buckets, sd["buckets"]):
             if s["npad"] != b.npad or (s["master"] is None) != (b.master is None):
                 raise ValueError("ZeRO shard checkpoint bucket layout differs")
@@ -551,7 +579,7 @@ class ZeroAdamW:
         """Optimizer-state bytes held by this rank (masters + moments of its shards)."""
         n = 0
         for b in self.buckets:
-            n += (b.exp_avg.numel() + b.exp_avg_sq.numel()) * 4
+            n += b.exp_avg.numel() * b.exp_avg.element_size() + b.exp_avg_sq.numel() * b.exp_avg_sq.element_size()
             n += b.master.numel() * 4 if b.master is not None else 0
         return n
 

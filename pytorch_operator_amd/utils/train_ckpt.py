@@ -54,6 +54,10 @@ def _cpu(x):
     return x
 
 
+def _dtype_name(dt) -> str:
+    return "bf16" if dt == torch.bfloat16 else "fp32"
+
+
 def optimizer_state(opt) -> dict:
     """Replicated optimizer state in a form that reloads without dtype casts: MasterAdamW keeps
     fp32 masters/moments for bf16 parameters, which ``Optimizer.load_state_dict`` would cast
@@ -61,7 +65,7 @@ def optimizer_state(opt) -> dict:
     from ..ops.optim import MasterAdamW
     if isinstance(opt, MasterAdamW):
         params = [p for g in opt.param_groups for p in g["params"]]
-        return {"kind": "master_adamw",
+        return {"kind": "master_adamw", "state_dtype": _dtype_name(opt.state_dtype),
                 "state": [{k: v for k, v in opt.state[p].items()} if p in opt.state else None for p in params]}
     return {"kind": "torch", "state_dict": opt.state_dict()}
 
@@ -71,6 +75,12 @@ def load_optimizer_state(opt, blob: dict) -> None:
         params = [p for g in opt.param_groups for p in g["params"]]
         if len(params) != len(blob["state"]):
             raise ValueError("checkpoint optimizer state does not match the parameters")
+        have = _dtype_name(opt.state_dtype)
+        got = blob.get("state_dtype", "fp32")  # checkpoints from before the field hold fp32 moments
+        held = {_dtype_name(st[k].dtype) for st in blob["state"] if st for k in ("exp_avg", "exp_avg_sq")}
+        if got != have or held - {have}:
+            raise ValueError(f"checkpoint holds {got} AdamW moments, the optimizer was built with {have} "
+                             "(state_dtype): they are never cast")
         for p, st in zip(params, blob["state"]):
             if st is None:
                 continue
