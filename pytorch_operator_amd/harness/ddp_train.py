@@ -17,11 +17,21 @@ kernels, fp32 all-reduce kept through a comm hook), DDP with flat gradient bucke
 (no gradient copy), optional bf16 gradient compression (``--allreduce-dtype bf16``), and
 the 288 GB HBM budget that lets Llama-3 8B train with plain DDP (whole fp32 model, grads
 and AdamW state per GPU -- no sharding).
+
+``--data PATH`` (Llama) trains on pre-tokenised files instead of the one synthetic batch: every
+micro-step reads its own windows (``data/tokens.py``), expanded on the device by
+``csrc/kernels/token_batch.hip``, with ``--lr-schedule`` / ``--lr-warmup-steps``, a held-out loss
+(``--eval-data``) and ``--log-every``:
+
+    python -m pytorch_operator_amd.harness.ddp_train --model llama3-8b --batch-size 4 --data shards/ \
+        --eos-id 128001 --lr-schedule cosine --lr-warmup-steps 200 --lr-total-steps 10000 \
+        --eval-data heldout.npy --eval-every 500 --log-every 50
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -112,7 +122,8 @@ def parse_args(argv=None):
                         "kernels of csrc/kernels/attention.hip) and the target after an end-of-text token is "
                         "ignored; 0 = off (one document per sequence)")
     p.add_argument("--eos-id", type=int, default=None,
-                   help="end-of-text token id for --doc-len-mean (default: the last vocabulary id)")
+                   help="end-of-text token id for --doc-len-mean (default: the last vocabulary id); with --data: "
+                        "turns the document mask on (no default)")
     p.add_argument("--grad-accum", type=int, default=1,
                    help="Llama: micro-batches of --batch-size sequences per optimizer step.  Master-weight / "
                         "ZeRO: their gradients are summed in fp32 accumulators (csrc/kernels/gradaccum.hip) and "
@@ -121,10 +132,48 @@ def parse_args(argv=None):
                    help="Llama, master-weight / ZeRO: dtype of the AdamW moments.  bf16 halves them (4 B per "
                         "parameter instead of 8) and the update pass rounds them stochastically, seeded by --seed "
                         "(csrc/kernels/adamw.hip); the master weights stay fp32")
+    p.add_argument("--data", default=None,
+                   help="Llama: train on pre-tokenised data -- a .npy / .bin file of token ids or a directory of "
+                        "them (data/tokens.py); every micro-step reads its own windows, expanded on the device "
+                        "by csrc/kernels/token_batch.hip.  With --eos-id, documents are masked in attention and "
+                        "the target after an end-of-text token is ignored; without it the stream is plain causal")
+    p.add_argument("--data-dtype", choices=["auto", "uint16", "uint32"], default="auto",
+                   help="--data: id width of .bin files (auto: uint16 when the vocabulary fits, else uint32)")
+    p.add_argument("--lr-schedule", choices=["constant", "cosine"], default="constant")
+    p.add_argument("--lr-warmup-steps", type=int, default=0,
+                   help="linear warm-up: lr*t/K for the optimizer steps t <= K")
+    p.add_argument("--lr-min-ratio", type=float, default=0.1,
+                   help="--lr-schedule cosine: the floor, as a fraction of --lr, reached at --lr-total-steps")
+    p.add_argument("--lr-total-steps", type=int, default=None,
+                   help="--lr-schedule cosine: length of the whole run in optimizer steps (a resumed run's --steps "
+                        "is not it)")
+    p.add_argument("--eval-data", default=None,
+                   help="--data: held-out token file(s); the eval loss is taken over its first "
+                        "--eval-batches * world * --batch-size windows, before the first step, every --eval-every "
+                        "steps and at the end")
+    p.add_argument("--eval-every", type=int, default=0)
+    p.add_argument("--eval-batches", type=int, default=8)
+    p.add_argument("--log-every", type=int, default=0,
+                   help="print a train event (step, loss, lr, grad_norm) every L optimizer steps; each one "
+                        "synchronises with the device")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
     args = p.parse_args(argv)
+    if args.data and not args.model.startswith("llama"):
+        p.error("--data is for the Llama models")
+    if args.data and args.doc_len_mean > 0:
+        p.error("--doc-len-mean draws synthetic documents; with --data the documents are the stream's (--eos-id)")
+    if args.eval_data and not args.data:
+        p.error("--eval-data needs --data")
+    if args.eval_data and args.eval_batches < 1:
+        p.error("--eval-batches: a positive number of batches")
+    if min(args.lr_warmup_steps, args.eval_every, args.log_every) < 0:
+        p.error("--lr-warmup-steps, --eval-every and --log-every are not negative")
+    if not 0.0 <= args.lr_min_ratio <= 1.0:
+        p.error("--lr-min-ratio: between 0 and 1")
+    if args.lr_schedule == "cosine" and (args.lr_total_steps is None or args.lr_total_steps <= args.lr_warmup_steps):
+        p.error("--lr-schedule cosine needs --lr-total-steps, larger than --lr-warmup-steps")
     if args.linear_dtype == "fp8" and not (args.model.startswith("llama") and args.dtype == "bf16"):
         p.error("--linear-dtype fp8 is for the Llama models with --dtype bf16")
     if args.grad_accum < 1:
@@ -332,6 +381,20 @@ def train_flops_per_sample(args) -> float:
     return (6 * n + attn) * args.seq_len  # per sequence
 
 
+def lr_at(t: int, lr: float, schedule: str = "constant", warmup: int = 0, min_ratio: float = 0.1,
+          total: int = None) -> float:
+    """Learning rate of optimizer step ``t`` (1-based): linear warm-up over the first ``warmup`` steps,
+    then constant, or a cosine from ``lr`` down to ``lr * min_ratio`` at step ``total`` and held there.
+    A pure function of the step: a resumed run needs no schedule state."""
+    if t <= warmup:
+        return lr * t / warmup
+    if schedule != "cosine":
+        return lr
+    if t >= total:
+        return lr * min_ratio
+    return lr * (min_ratio + (1 - min_ratio) * 0.5 * (1 + math.cos(math.pi * (t - warmup) / (total - warmup))))
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -366,7 +429,28 @@ def main(argv=None) -> int:
         elif use_master_weights(args, dev):
             model.register_comm_hook(None, fp32_allreduce_hook)
     g = torch.Generator(device="cpu").manual_seed(args.seed + rank)
-    if is_llama:
+    feed = eval_feed = None
+    if args.data:
+        # token files: every micro-step takes its own windows (data/tokens.py, data/feed.py)
+        from ..data.feed import TokenFeed
+        from ..data.tokens import TokenStream
+        from ..models.llama import CONFIGS
+        V = CONFIGS[args.model].vocab_size
+        try:
+            if args.eos_id is not None and not 0 <= args.eos_id < V:
+                raise ValueError(f"--eos-id {args.eos_id}: an id of the {V}-token vocabulary")
+            feed = TokenFeed(TokenStream(args.data, V, args.data_dtype).bind(args.seq_len, B, N, world),
+                             rank, dev, args.eos_id)
+            if args.eval_data:
+                eval_feed = TokenFeed(TokenStream(args.eval_data, V, args.data_dtype)
+                                      .bind(args.seq_len, B, args.eval_batches, world), rank, dev, args.eos_id)
+        except ValueError as e:
+            print(f"error: {e}", file=sys.stderr, flush=True)
+            if world > 1:
+                dist.destroy_process_group()
+            return 2
+        doc_start = None
+    elif is_llama:
         from ..models.llama import CONFIGS
         V = CONFIGS[args.model].vocab_size
         if args.doc_len_mean > 0:
@@ -416,12 +500,74 @@ def main(argv=None) -> int:
 
     own_accum = hasattr(opt, "accumulate")  # MasterAdamW / ZeroAdamW: fp32 accumulators
 
+    def fed(f, t, k, n, last=None):
+        """Micro-batch ``k`` of ``n`` of step ``t`` from a token feed, the next one copied ahead
+        (``last``: the step after which nothing follows); the kernel's bounds go to attention."""
+        then = (t, k + 1) if k + 1 < n else (None if t == last else (t + 1, 0))
+        xk, yk, ds, de, stats = f.take(t, k, then)
+        if ds is not None and use_gpu:
+            from ..ops.attention import set_doc_bounds
+            set_doc_bounds(ds, de)
+        return xk, yk, ds, stats
+
+    base_lr = args.lr or 3e-4
+    scheduled = args.lr_schedule != "constant" or args.lr_warmup_steps > 0
+    cur_lr = base_lr
+
+    def set_lr(t):
+        nonlocal cur_lr
+        cur_lr = lr_at(t, base_lr, args.lr_schedule, args.lr_warmup_steps, args.lr_min_ratio, args.lr_total_steps)
+        if hasattr(opt, "set_lr"):
+            opt.set_lr(cur_lr)
+        else:
+            for group in opt.param_groups:
+                group["lr"] = cur_lr
+
+    def evaluate():
+        """Token-weighted loss over the eval stream's first --eval-batches * world * B windows."""
+        was_training = bare.training
+        bare.eval()
+        acc = torch.zeros(2, dtype=torch.float64, device=dev)
+        with torch.no_grad():
+            for k in range(args.eval_batches):
+                xk, yk, dk, stats = fed(eval_feed, 1, k, args.eval_batches, last=1)
+                with amp:
+                    lk = bare(xk, yk) if dk is None else bare(xk, yk, doc_start=dk)
+                acc[0] += lk.double() * stats[0]
+                acc[1] += stats[0]
+        bare.train(was_training)
+        if world > 1:
+            dist.all_reduce(acc)
+        loss_sum, tokens = (float(v) for v in acc.cpu())
+        ev = loss_sum / max(tokens, 1.0)
+        if rank == 0:
+            print(json.dumps({"event": "eval", "step": gstep, "loss": ev, "ppl": math.exp(min(ev, 700.0)),
+                              "tokens": int(tokens)}), flush=True)
+        return ev
+
+    def bad_ids() -> int:
+        """Ids >= the vocabulary seen so far, over all ranks (reads the device: call at a sync point)."""
+        bad = torch.stack([f.total[2] for f in (feed, eval_feed) if f is not None]).sum()
+        if world > 1:
+            dist.all_reduce(bad)
+        n = int(bad)
+        if n:
+            print(f"error: {n} token id(s) >= the vocabulary size {V} in the data (each was clamped to {V - 1}): "
+                  "wrong --data-dtype, or files of another tokenizer", file=sys.stderr, flush=True)
+            if world > 1:
+                dist.destroy_process_group()
+        return n
+
     def accum_backward():
         """N x (forward, backward); returns the mean of the micro-batch losses (on the device)."""
         total = None
-        for k, (xk, yk, dk) in enumerate(micro):
+        for k in range(N):
+            xk, yk, dk = fed(feed, gstep, k, N)[:3] if feed is not None else micro[k]
             with amp:
                 lk = model(xk, yk) if dk is None else model(xk, yk, doc_start=dk)
+            if N == 1:
+                lk.backward()
+                return lk
             if own_accum:
                 lk.backward()
                 if k < N - 1:
@@ -437,7 +583,9 @@ def main(argv=None) -> int:
         if args.ckpt_dir and args.ckpt_every and gstep % args.ckpt_every == 0:
             pending_ckpt.append(gstep)
         opt.zero_grad(set_to_none=True)
-        if N > 1:
+        if scheduled:
+            set_lr(gstep)
+        if N > 1 or feed is not None:
             loss = accum_backward()
         else:
             with amp:
@@ -461,17 +609,43 @@ def main(argv=None) -> int:
         if use_gpu:
             torch.cuda.synchronize(dev)
 
+    eval_loss = None
+
+    def after_step(loss) -> int:
+        """--log-every / --eval-every (the only added host syncs); non-zero: ids >= vocab, stop."""
+        nonlocal eval_loss
+        synced = False
+        if args.log_every and gstep % args.log_every == 0:
+            ev = {"event": "train", "rank": rank, "step": gstep, "loss": float(loss), "lr": cur_lr}
+            if clip is not None:
+                ev["grad_norm"] = grad_norm()
+            print(json.dumps(ev), flush=True)
+            synced = True
+        if eval_feed is not None and args.eval_every and gstep % args.eval_every == 0:
+            eval_loss = evaluate()
+            synced = True
+        return 2 if synced and feed is not None and bad_ids() else 0
+
+    if eval_feed is not None:
+        eval_loss = evaluate()  # the starting point (step 0, or the checkpoint's step)
+        if bad_ids():
+            return 2
     t_start = time.time_ns()
     loss = step()
     sync()
+    if feed is not None and bad_ids():
+        return 2
     if rank == 0:
         first = {"event": "first_step", "rank": rank, "unix_ns": time.time_ns(),
                  "first_step_s": round((time.time_ns() - t_start) / 1e9, 3), "loss": float(loss)}
         if clip is not None:
             first["grad_norm"] = grad_norm()
         print(json.dumps(first), flush=True)
+    if after_step(loss):
+        return 2
     for _ in range(max(0, args.warmup - 1)):
-        step()
+        if after_step(step()):
+            return 2
     sync()
     if world > 1:
         dist.barrier()
@@ -479,6 +653,8 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
+        if after_step(loss):
+            return 2
     sync()
     if world > 1:
         dist.barrier()
@@ -488,6 +664,10 @@ def main(argv=None) -> int:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if eval_feed is not None and not (args.eval_every and gstep % args.eval_every == 0):
+        eval_loss = evaluate()
+    if feed is not None and bad_ids():
+        return 2
     samples = args.steps * B * world * N
     per_sample = train_flops_per_sample(args)
     unit_tokens = is_llama
@@ -495,7 +675,8 @@ def main(argv=None) -> int:
     res = {"metric": f"{args.model.replace('-', '_')}_ddp_train_{'tokens' if unit_tokens else 'images'}_per_sec",
            "value": round(value, 1), "unit": "tokens/s" if unit_tokens else "images/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-           "dtype": args.dtype, "data": "synthetic", "params": n_params, "per_rank_batch": B,
+           "dtype": args.dtype, "data": "tokens" if feed is not None else "synthetic", "params": n_params,
+           "per_rank_batch": B,
            "seq_len": args.seq_len if is_llama else None, "loss": float(loss),
            "tflops_per_gpu": round(per_sample * samples / dt / world / 1e12, 1) if per_sample else None,
            "max_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1) if use_gpu else None,
@@ -518,6 +699,14 @@ def main(argv=None) -> int:
         res.update(opt_state=args.opt_state, optimizer_state_bytes=optimizer_state_bytes(opt))
     if is_llama and doc_start is not None:
         res.update(doc_len_mean=args.doc_len_mean, docs_per_seq=round(docs_per_seq, 2), attn_mask="document")
+    if feed is not None:
+        st = feed.stream
+        res.update(data_tokens=st.n_tokens, data_windows=st.n_windows,
+                   data_epochs=round(gstep * N * world * B / st.n_windows, 4), lr_schedule=args.lr_schedule)
+        if args.eos_id is not None:
+            res.update(attn_mask="document", docs_per_seq=round(float(feed.total[1]) / max(1, feed.batches * B), 2))
+    if eval_loss is not None:
+        res.update(eval_loss=eval_loss)
     if tuning.get("mode") == "tune" and rank == 0:
         import torch.cuda.tunable as tunable
         out = args.gemm_tuning_file or default_tuning_file()

@@ -206,6 +206,8 @@ _SIGNATURES = {
     "pto_grad_sumsq_finish": [_VP, _L, _VP, _VP],
     # gradaccum.hip
     "pto_grad_accum": [_VP, _VP, _VP, _L, _I, _I, _VP],
+    # token_batch.hip
+    "pto_token_batch": [_VP, _I, _L, _I, _I, _L, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     # fp8_cast.hip
     "pto_fp8_amax":[_VP, _L, _L, _VP, _L, _VP],
     "pto_fp8_cast": [_VP, _L, _L, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP],
@@ -237,7 +239,7 @@ _SIGNATURES = {
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
              "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
-             "pto_grad_accum_sweep": []}
+             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": []}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

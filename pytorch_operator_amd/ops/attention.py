@@ -202,6 +202,19 @@ def _doc_bounds(doc_start: torch.Tensor):
     return ds, de
 
 
+def set_doc_bounds(doc_start: torch.Tensor, doc_end: torch.Tensor) -> None:
+    """Prime the one-entry bounds cache with bounds that are correct by construction (the batch
+    kernel of ``ops/token_batch.py`` writes both): ``flash_attention(..., doc_start=doc_start)`` with
+    this very tensor, unedited, then uses ``doc_end`` as given and calls neither ``doc_ends`` nor
+    ``validate_doc_start``."""
+    global _doc_bounds_cache
+    if (doc_start.dtype != torch.int32 or doc_end.dtype != torch.int32 or doc_start.dim() != 2
+            or doc_start.shape != doc_end.shape or doc_start.device != doc_end.device
+            or not doc_start.is_contiguous() or not doc_end.is_contiguous()):
+        raise ValueError("set_doc_bounds: two contiguous int32 [B, S] tensors on one device")
+    _doc_bounds_cache = (doc_start, doc_start._version, doc_start, doc_end)
+
+
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                     doc_start: torch.Tensor = None) -> torch.Tensor:
     if doc_start is not None:

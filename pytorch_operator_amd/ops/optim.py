@@ -152,6 +152,12 @@ class MasterAdamW(torch.optim.Optimizer):
         synchronise: with ``overlap=True`` the value is written on the side stream."""
         return None if self._clip is None else self._clip.last_grad_norm()
 
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the next ``step()`` (a schedule sets it per step: the fused launch
+        takes it as a host scalar)."""
+        for group in self.param_groups:
+            group["lr"] = lr
+
     def _state(self, p):
         st = self.state[p]
         if not st:

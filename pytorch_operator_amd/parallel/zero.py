@@ -493,6 +493,11 @@ class ZeroAdamW:
         step).  Does not synchronise."""
         return None if self._clip is None else self._clip.last_grad_norm()
 
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the next ``step()`` (a schedule sets it per step: the fused launch
+        takes it as a host scalar)."""
+        self.lr = lr
+
     @staticmethod
     def _save_ranges(b: _Bucket, ranges) -> list:
         """Copies of the optimizer state + weights of the bucket ranges AdamW must not touch
