@@ -39,6 +39,22 @@ import time
 MODELS = ("resnet50", "resnet-tiny", "llama3-8b", "llama3-1b", "llama-tiny", "llama-mini", "llama-mini64")
 
 
+def parse_prompt(text, vocab_size: int):
+    """'id,id,...' -> [ids] (None stays None); ValueError for anything but ids of the vocabulary."""
+    if text is None:
+        return None
+    try:
+        ids = [int(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise ValueError(f"token ids separated by commas, got {text!r}") from None
+    if not ids:
+        raise ValueError("at least one token id")
+    bad = [i for i in ids if not 0 <= i < vocab_size]
+    if bad:
+        raise ValueError(f"ids {bad[:4]} are outside the {vocab_size}-token vocabulary")
+    return ids
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="DDP training worker (ResNet-50 / Llama-3, synthetic data)")
     p.add_argument("--model", choices=MODELS, default="resnet50")
@@ -156,10 +172,46 @@ def parse_args(argv=None):
     p.add_argument("--log-every", type=int, default=0,
                    help="print a train event (step, loss, lr, grad_norm) every L optimizer steps; each one "
                         "synchronises with the device")
+    p.add_argument("--sample-every", type=int, default=0,
+                   help="Llama: every K optimizer steps and at the end, continue --sample-prompt by --sample-tokens "
+                        "tokens (Llama.generate: KV cache + csrc/kernels/decode_attention.hip) and print a sample "
+                        "event; every rank generates the same text, rank 0 prints it; 0 = off (a K above the run's "
+                        "length samples at the end alone).  The other --sample-* flags need it")
+    p.add_argument("--sample-tokens", type=int, default=32, help="--sample-every: new tokens per sample")
+    p.add_argument("--sample-prompt", default=None,
+                   help="--sample-every: token ids 'id,id,...' (default with --data: the first --sample-prompt-len "
+                        "ids of the eval stream's first window, or the train stream's; without --data: ids "
+                        "1..--sample-prompt-len, clamped to the vocabulary)")
+    p.add_argument("--sample-prompt-len", type=int, default=16,
+                   help="--sample-every: length of the default prompt (not with --sample-prompt)")
+    p.add_argument("--sample-temperature", type=float, default=0.0, help="--sample-every: 0 = greedy")
+    p.add_argument("--sample-top-k", type=int, default=0, help="--sample-every: 0 = the whole vocabulary")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
     args = p.parse_args(argv)
+    sampling = [f for f, v, d in (("--sample-every", args.sample_every, 0), ("--sample-tokens", args.sample_tokens, 32),
+                                  ("--sample-prompt", args.sample_prompt, None),
+                                  ("--sample-prompt-len", args.sample_prompt_len, 16),
+                                  ("--sample-temperature", args.sample_temperature, 0.0),
+                                  ("--sample-top-k", args.sample_top_k, 0)) if v != d]
+    if sampling and not args.model.startswith("llama"):
+        p.error(f"{sampling[0]} is for the Llama models")
+    args.sample_prompt_ids = None
+    if sampling:
+        if args.sample_every == 0:
+            p.error(f"{sampling[0]} needs --sample-every K (K > 0): without it nothing is sampled")
+        if args.sample_prompt is not None and args.sample_prompt_len != 16:
+            p.error("--sample-prompt-len sets the length of the default prompt: not with --sample-prompt")
+        from ..models.llama import CONFIGS
+        try:
+            args.sample_prompt_ids = parse_prompt(args.sample_prompt, CONFIGS[args.model].vocab_size)
+        except ValueError as e:
+            p.error(f"--sample-prompt: {e}")
+        if args.sample_every < 0 or args.sample_tokens < 1 or args.sample_prompt_len < 1:
+            p.error("--sample-every is not negative; --sample-tokens and --sample-prompt-len are positive")
+        if args.sample_temperature < 0 or not 0 <= args.sample_top_k <= CONFIGS[args.model].vocab_size:
+            p.error("--sample-temperature is not negative; --sample-top-k is between 0 and the vocabulary size")
     if args.data and not args.model.startswith("llama"):
         p.error("--data is for the Llama models")
     if args.data and args.doc_len_mean > 0:
@@ -545,6 +597,34 @@ def main(argv=None) -> int:
                               "tokens": int(tokens)}), flush=True)
         return ev
 
+    sampling = is_llama and args.sample_every > 0
+    if sampling:
+        # the same prompt and seed on every rank: each generates the same text, no collectives
+        prompt_ids = args.sample_prompt_ids
+        if prompt_ids is None and feed is not None:
+            st = (eval_feed or feed).stream
+            prompt_ids = [min(int(t), V - 1) for t in st.read(0, min(args.sample_prompt_len, st.seq_len))]
+        elif prompt_ids is None:
+            prompt_ids = [min(i, V - 1) for i in range(1, args.sample_prompt_len + 1)]
+        if len(prompt_ids) + args.sample_tokens > bare.cfg.max_seq_len:
+            print(f"error: a prompt of {len(prompt_ids)} ids and --sample-tokens {args.sample_tokens} exceed the "
+                  f"model's {bare.cfg.max_seq_len} positions", file=sys.stderr, flush=True)
+            if world > 1:
+                dist.destroy_process_group()
+            return 2
+        sample_gen = torch.Generator(device=dev).manual_seed(args.seed) if args.sample_temperature > 0 else None
+
+    def sample():
+        """Continue the prompt (Llama.generate); touches neither the data generator, the feeds, the
+        optimizer nor the gradients.  The KV cache lives for the call."""
+        with amp:
+            toks = bare.generate(torch.tensor([prompt_ids], dtype=torch.long, device=dev),
+                                 max_new_tokens=args.sample_tokens, temperature=args.sample_temperature,
+                                 top_k=args.sample_top_k, generator=sample_gen)
+        if rank == 0:
+            print(json.dumps({"event": "sample", "step": gstep, "prompt": prompt_ids, "tokens": toks[0].tolist()}),
+                  flush=True)
+
     def bad_ids() -> int:
         """Ids >= the vocabulary seen so far, over all ranks (reads the device: call at a sync point)."""
         bad = torch.stack([f.total[2] for f in (feed, eval_feed) if f is not None]).sum()
@@ -624,6 +704,9 @@ def main(argv=None) -> int:
         if eval_feed is not None and args.eval_every and gstep % args.eval_every == 0:
             eval_loss = evaluate()
             synced = True
+        if sampling and args.sample_every and gstep % args.sample_every == 0:
+            sample()
+            synced = True
         return 2 if synced and feed is not None and bad_ids() else 0
 
     if eval_feed is not None:
@@ -666,6 +749,8 @@ def main(argv=None) -> int:
         dt = float(t.item())
     if eval_feed is not None and not (args.eval_every and gstep % args.eval_every == 0):
         eval_loss = evaluate()
+    if sampling and not (args.sample_every and gstep % args.sample_every == 0):
+        sample()
     if feed is not None and bad_ids():
         return 2
     samples = args.steps * B * world * N

@@ -17,12 +17,16 @@ The elementwise work between the matmuls runs as hand-written HIP kernels on a G
 RMSNorm (``ops.norm``, fp32 statistics over the fp32 residual stream, bf16 output under
 autocast so the next matmul reads it directly), RoPE and SwiGLU (``ops.llm``, one HBM pass
 each, fwd and bwd).  On CPU the same math runs in PyTorch.
+
+``Llama.generate`` writes text: ``prefill`` fills a KV cache from the prompts, ``decode_step`` appends
+one token per sequence and attends over the cache with the single-query HIP kernels of ``ops.decode``.
 """
 from __future__ import annotations
 
+import collections
 import math
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -129,8 +133,28 @@ class TNLinear(nn.Linear):
         return super().forward(x)
 
 
+class LayerCache(NamedTuple):
+    """One layer's view of an ``ops.decode.KVCache`` for one forward: ``k``, ``v`` [B, max_len, Hkv, D];
+    a decode step also needs ``pos`` (the row to append at), ``lens`` (valid rows after the append),
+    both int32 [B] on the device, and the host-known bound ``max_keys``.  A prefill leaves them None."""
+    k: torch.Tensor
+    v: torch.Tensor
+    pos: Optional[torch.Tensor]
+    lens: Optional[torch.Tensor]
+    max_keys: Optional[int]
+
+
 class Attention(nn.Module):
+    """GQA attention with RoPE.  Which kernels run is chosen per call, for the prefill / training path
+    and for the decode step alike: the hand-written HIP ones where the shape and dtype are theirs (bf16,
+    head dim 64 or 128, ...), the library's ``scaled_dot_product_attention`` otherwise -- an fp32 model
+    called without autocast, for instance, runs the library path on a GPU without an error (the
+    ``ops`` wrappers themselves never fall back).  ``decode_calls`` counts the decode steps per path
+    ("hip", "sdpa", "cpu"), so that a benchmark or a test can assert which one it ran."""
+
     impl = "auto"  # "auto": HIP flash attention where it applies; "sdpa": library kernels
+    decode_impl = None  # the decode step alone: None follows impl; "sdpa" / "auto" for A/B runs (tools/decode_bench.py)
+    decode_calls = collections.Counter()
 
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -140,11 +164,25 @@ class Attention(nn.Module):
         self.wqkv = TNLinear(cfg.dim, (self.nh + 2 * self.nkv) * self.hd)
         self.wo = TNLinear(self.nh * self.hd, cfg.dim)
 
-    def forward(self, x, cos, sin, doc_start=None):
+    def forward(self, x, cos, sin, doc_start=None, cache=None):
+        """``cache`` (a ``LayerCache``): S > 1 is a prefill -- the rotated k and v also go to the layer's
+        cache rows [0, S); S == 1 is a decode step -- k and v are appended at row ``cache.pos[b]`` and
+        the one query attends to the ``cache.lens[b]`` rows of the cache (``ops.decode``)."""
         B, S, _ = x.shape
         from ..ops import attention as A
         from ..ops.llm import rope_qkv
+        if cache is not None and S == 1:
+            from ..ops import decode as Dc
+            q = Dc.rope_append(self.wqkv(x).reshape(B, -1), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv)
+            hip = (self.decode_impl or self.impl) != "sdpa" and (not q.is_cuda or Dc.hip_supported(q, cache.k, cache.v))
+            Attention.decode_calls["cpu" if not q.is_cuda else ("hip" if hip else "sdpa")] += 1
+            o = Dc.decode_attention(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa")
+            return self.wo(o.reshape(B, 1, self.nh * self.hd))
         q, k, v = rope_qkv(self.wqkv(x), cos, sin, self.nh, self.nkv)
+        if cache is not None:
+            n = min(S, cache.k.shape[1])  # a prompt padded to the attention kernels' multiple may end past the cache
+            cache.k[:, :n].copy_(k[:, :n])
+            cache.v[:, :n].copy_(v[:, :n])
         if doc_start is not None:
             # packed documents: attention stays inside each one; RoPE positions stay absolute
             # (it is relative, so restarting them per document would change nothing)
@@ -179,12 +217,12 @@ class Block(nn.Module):
         self.ffn_norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x, delta, cos, sin, doc_start=None):
+    def forward(self, x, delta, cos, sin, doc_start=None, cache=None):
         """x: residual stream entering the block minus the previous block's FFN output
         ``delta`` (None for the first block): each residual add happens inside the next
         RMSNorm.  Returns (residual stream before the FFN add, FFN output)."""
         h, y = self.attention_norm.add_forward(x, delta)
-        h, y = self.ffn_norm.add_forward(h, self.attention(y, cos, sin, doc_start))
+        h, y = self.ffn_norm.add_forward(h, self.attention(y, cos, sin, doc_start, cache))
         return h, self.feed_forward(y)
 
 
@@ -227,3 +265,136 @@ class Llama(nn.Module):
         from ..ops.llm import cross_entropy
         # the logits are this op's own intermediate: d(logits) may overwrite them
         return cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1), overwrite_logits=True)
+
+    # ------------------------------------------------------------------ generation (ops.decode)
+    def _low_precision(self, device) -> bool:
+        """The projections run in bf16: under autocast, or with bf16 matmul weights."""
+        return torch.is_autocast_enabled(device.type) or self.layers[0].attention.wqkv.weight.dtype == torch.bfloat16
+
+    def new_cache(self, B: int, max_len: int, dtype=None):
+        """An empty ``ops.decode.KVCache`` for ``B`` sequences of up to ``max_len`` tokens, in the dtype
+        the projections write (bf16 under autocast or with bf16 weights, else the weights' own)."""
+        from ..ops.decode import KVCache
+        w = self.layers[0].attention.wqkv.weight
+        if dtype is None:
+            dtype = torch.bfloat16 if self._low_precision(w.device) else w.dtype
+        return KVCache(self.cfg.n_layers, B, max_len, self.cfg.n_kv_heads, self.cfg.head_dim, dtype, w.device)
+
+    def _rope(self, cache, rows: int):
+        if cache.rope is None or cache.rope[0].shape[0] < rows:
+            cache.rope = rope_tables(self.cfg.head_dim, rows, self.cfg.rope_theta, cache.k.device)
+        return cache.rope
+
+    def _prefill_len(self, P: int, device) -> int:
+        """The length a prompt of P tokens is run at: on a GPU with the HIP attention on, the next multiple
+        of its tile (it takes whole tiles; causal masking hides the padding from every prompt token)."""
+        from ..ops import attention as A
+        if device.type == "cuda" and Attention.impl != "sdpa" and self.cfg.head_dim in A.HEAD_DIMS:
+            return -(-P // A.SEQ_MULTIPLE) * A.SEQ_MULTIPLE
+        return P
+
+    def prefill(self, tokens: torch.Tensor, prompt_lens: torch.Tensor, cache) -> torch.Tensor:
+        """Run the right-padded prompts ``tokens`` [B, P] (row b holds ``prompt_lens[b]`` >= 1 tokens),
+        fill the cache and return the logits [B, V] after each row's last prompt token.  The hidden state
+        is gathered at ``prompt_lens - 1`` before the final norm, so no [B, P, V] logits exist.  Cache
+        rows at and past ``prompt_lens[b]`` hold padding; they are masked by ``cache.lens`` and
+        overwritten by later appends."""
+        B, P = tokens.shape
+        S = self._prefill_len(P, tokens.device)
+        if S > P:
+            tokens = F.pad(tokens, (0, S - P))
+        cos, sin = self._rope(cache, max(S, cache.max_len))
+        cos, sin = cos[:S], sin[:S]
+        h, d = self.tok_embeddings(tokens), None
+        for i, blk in enumerate(self.layers):
+            h, d = blk(h, d, cos, sin, None, LayerCache(cache.k[i], cache.v[i], None, None, None))
+        rows, last = torch.arange(B, device=tokens.device), prompt_lens.to(tokens.device).long() - 1
+        logits = self.output(self.norm.add_forward(h[rows, last].unsqueeze(1), d[rows, last].unsqueeze(1))[1])
+        cache.lens = prompt_lens.to(device=tokens.device, dtype=torch.int32).clone()
+        return logits[:, 0]
+
+    def decode_step(self, tokens: torch.Tensor, cache, max_keys: Optional[int] = None) -> torch.Tensor:
+        """Append one token per row (``tokens`` [B]) at position ``cache.lens`` and return the logits
+        [B, V] of the next one.  ``max_keys``: a host-known upper bound of the lengths after the append
+        (default: the cache's size); it alone sets the attention grid, nothing is read from the device."""
+        pos = cache.lens
+        lens = pos + 1
+        mk = cache.max_len if max_keys is None else max_keys
+        cos, sin = self._rope(cache, cache.max_len)
+        h, d = self.tok_embeddings(tokens).unsqueeze(1), None
+        for i, blk in enumerate(self.layers):
+            h, d = blk(h, d, cos, sin, None, LayerCache(cache.k[i], cache.v[i], pos, lens, mk))
+        logits = self.output(self.norm.add_forward(h, d)[1])
+        cache.lens = lens
+        return logits[:, 0]
+
+    def generate(self, prompts: torch.Tensor, prompt_lens=None, max_new_tokens: int = 32, temperature: float = 0.0,
+                 top_k: int = 0, eos_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
+                 return_logits: bool = False, max_len: Optional[int] = None):
+        """Continue ``prompts`` [B, P] (right-padded; ``prompt_lens`` [B], default all P) by
+        ``max_new_tokens`` tokens: LongTensor [B, max_new_tokens] (and the fp32 logits [B, T, V] each was
+        chosen from, with ``return_logits``).  Greedy at temperature 0, else temperature / top-k sampling
+        with ``torch.multinomial`` from ``generator``; a row that has emitted ``eos_id`` keeps emitting it.
+        Runs without gradients in eval mode with bf16 projections on a GPU (never FP8).  The token loop
+        reads nothing back from the device; the one synchronisation is the caller's use of the result."""
+        V = self.cfg.vocab_size
+        if not isinstance(prompts, torch.Tensor) or prompts.dim() != 2 or prompts.dtype != torch.long or \
+                prompts.shape[1] < 1:
+            raise ValueError("generate: prompts must be a LongTensor [B, P] with P >= 1")
+        B, P = prompts.shape
+        T = max_new_tokens
+        if not isinstance(T, int) or T < 1:
+            raise ValueError(f"generate: max_new_tokens must be a positive int, got {T!r}")
+        if not temperature >= 0.0 or not math.isfinite(temperature):
+            raise ValueError(f"generate: temperature must be finite and >= 0, got {temperature!r}")
+        if not isinstance(top_k, int) or not 0 <= top_k <= V:
+            raise ValueError(f"generate: top_k must be in [0, {V}] (0 = off), got {top_k!r}")
+        if eos_id is not None and not 0 <= eos_id < V:
+            raise ValueError(f"generate: eos_id {eos_id} is not an id of the {V}-token vocabulary")
+        max_len = P + T if max_len is None else max_len
+        if not P + T <= max_len <= self.cfg.max_seq_len:
+            raise ValueError(f"generate: need P + max_new_tokens = {P + T} <= max_len = {max_len} <= "
+                             f"max_seq_len = {self.cfg.max_seq_len}")
+        # host-side checks of the prompt, before the loop
+        host_lens = [P] * B if prompt_lens is None else [int(n) for n in torch.as_tensor(prompt_lens).cpu().tolist()]
+        if len(host_lens) != B or min(host_lens) < 1 or max(host_lens) > P:
+            raise ValueError(f"generate: prompt_lens must be {B} lengths in [1, {P}], got {host_lens}")
+        pc = prompts.cpu()
+        if int(pc.min()) < 0 or int(pc.max()) >= V:
+            raise ValueError(f"generate: prompt ids must be in [0, {V})")
+        dev = self.tok_embeddings.weight.device
+        prompts = prompts.to(dev)
+        lens = torch.tensor(host_lens, dtype=torch.int32, device=dev)
+        amp_on = dev.type == "cuda" or self._low_precision(dev)
+        was_training, linear_impl = self.training, TNLinear.impl
+        self.eval()
+        if TNLinear.impl == "fp8":
+            TNLinear.impl = "tn"
+        try:
+            with torch.no_grad(), torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=amp_on):
+                cache = self.new_cache(B, max_len, torch.bfloat16 if amp_on else None)
+                self._rope(cache, max(max_len, self._prefill_len(P, dev)))  # the tables, once: the padded prompt's too
+                logits = self.prefill(prompts, lens, cache).float()
+                out, kept = [], []
+                done = torch.zeros(B, dtype=torch.bool, device=dev)
+                for t in range(T):
+                    if temperature == 0.0:
+                        nxt = logits.argmax(-1)
+                    else:
+                        z = logits / temperature
+                        if top_k:
+                            z = torch.where(z < z.topk(top_k, dim=-1).values[:, -1:], -math.inf, z)
+                        nxt = torch.multinomial(torch.softmax(z, dim=-1), 1, generator=generator)[:, 0]
+                    if eos_id is not None:
+                        nxt = torch.where(done, eos_id, nxt)
+                        done = done | (nxt == eos_id)
+                    out.append(nxt)
+                    if return_logits:
+                        kept.append(logits)
+                    if t + 1 < T:
+                        logits = self.decode_step(nxt, cache, max_keys=P + t + 1).float()
+        finally:
+            TNLinear.impl = linear_impl
+            self.train(was_training)
+        tokens = torch.stack(out, dim=1)
+        return (tokens, torch.stack(kept, dim=1)) if return_logits else tokens

@@ -194,6 +194,9 @@ _SIGNATURES = {
     "pto_transpose16": [_VP, _VP, _L, _L, _VP],
     "pto_xent_fwd": [_VP, _VP, _VP, _VP, _L, _I, _L, _I, _VP],
     "pto_xent_bwd": [_VP, _VP, _VP, _VP, _VP, _L, _I, _L, _I, _VP],
+    # decode_attention.hip
+    "pto_rope_append": [_VP] * 7 + [_L, _I, _I, _I, _I, _I, _I, _VP],
+    "pto_decode_attn": [_VP] * 8 + [_I] * 7 + [_VP],
     # adamw.hip
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
     "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
@@ -239,7 +242,7 @@ _SIGNATURES = {
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
              "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
-             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": []}
+             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": []}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

@@ -141,6 +141,25 @@ def save(dirpath: str, step: int, model, opt, rank: int, world: int, keep: int =
     _barrier(world)
 
 
+def load_weights(dirpath: str, model, device) -> int:
+    """Load the weights alone of the last complete checkpoint (``meta.json`` and ``model.pt`` only: sharded
+    and replicated checkpoints alike, ``model.pt`` is always rank 0's full weights); returns its step.
+    Each parameter takes the dtype the checkpoint holds it in (bf16 matmul weights of a master-weight run)."""
+    meta_path = os.path.join(dirpath, "meta.json")
+    if not os.path.exists(meta_path):
+        raise ValueError(f"{dirpath}: no checkpoint (meta.json is missing)")
+    with open(meta_path) as f:
+        meta = json.load(f)
+    path = os.path.join(dirpath, meta["subdir"]) if meta.get("subdir") else dirpath
+    sd = torch.load(os.path.join(path, "model.pt"), map_location=device, weights_only=True)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if name in sd and sd[name].dtype != p.dtype:
+                p.data = p.data.to(sd[name].dtype)
+        model.load_state_dict(sd)
+    return int(meta["step"])
+
+
 def load(dirpath: Optional[str], model, opt, rank: int, world: int, device) -> int:
     """Restore the last checkpoint in ``dirpath`` (if any); returns the step it was taken at (0: none)."""
     if not dirpath or not os.path.exists(os.path.join(dirpath, "meta.json")):
