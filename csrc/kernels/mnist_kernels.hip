@@ -1984,7 +1984,10 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
   if (e_x >= 0 && e_x < 196) xvv = reinterpret_cast<const float4*>(xn)[(size_t)bo * 196 + e_x];
   if (tid < 45) ivv = reinterpret_cast<const uint4*>(idx1)[(size_t)bo * 180 + cig * 45 + tid];
   stamp_entry(dbg, t0);
-  __shared__ unsigned s_grp[2];  // group arrival counters (waves 0-7, waves 8-15)
+  // group arrival counters [0] (waves 0-7), [1] (waves 8-15) in 16 bytes of static LDS: the
+  // dynamic array starts behind them, and behind two counters' 8 bytes every float4 LDS access of
+  // this kernel (the W2-slice staging stores, pk_s) was misaligned (round 8: stage 2.08 -> 1.61 us)
+  __shared__ __attribute__((aligned(16))) unsigned s_grp[4];
   if (tid == 0) {
     s_grp[0] = 0u;
     s_grp[1] = 0u;
