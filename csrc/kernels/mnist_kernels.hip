@@ -2513,6 +2513,14 @@ inline BatchSrc make_src(const void* x, int is_u8, const int* labels, const int*
   return s;
 }
 
+// batch_row / batch_row_at wrap at most once past the end of the permutation: a batch larger than
+// the dataset, or a host offset outside it, would index perm[] and the pixels out of bounds.
+inline bool batch_in_range(const int* perm, const int* cursor, int host_offset, int n_total, int B) {
+  if (perm == nullptr) return true;
+  if (n_total <= 0 || B > n_total) return false;
+  return cursor != nullptr || (host_offset >= 0 && host_offset < n_total);
+}
+
 // Phase-timestamp buffer (tools/phase_profile.py, tools/step_timeline.py); null in production.
 // Every launch takes the next of kDbgSlots slots of kDbgSlotU64 words (<= 1024 blocks x 16), so
 // the kernels of one captured step stamp disjoint regions.
@@ -2621,7 +2629,7 @@ int pto_mnist_conv1_fwd(const void* x, int is_u8, const int* labels, const int* 
                         int B, float* zero_ptr, int zero_n, float* xn_out, int* lab_out,
                         void* stream) {
   PTO_CHECK_B(B);
-  if (perm != nullptr && n_total <= 0) return -1;
+  if (!batch_in_range(perm, cursor, host_offset, n_total, B)) return -1;
   if (lab_out != nullptr && labels == nullptr) return -1;
   const BatchSrc src = make_src(x, is_u8, labels, perm, cursor, host_offset, n_total, scale, shift);
   const int blocks = (B * 2880 + 255) / 256;
@@ -2647,7 +2655,7 @@ int pto_mnist_conv12_fwd(const void* x, int is_u8, const int* labels, const int*
                          const int* stg_tag, void* stream) {
   PTO_CHECK_B(B);
   if (B > 65535) return -1;  // grid y
-  if (perm != nullptr && n_total <= 0) return -1;
+  if (!batch_in_range(perm, cursor, host_offset, n_total, B)) return -1;
   if (lab_out != nullptr && labels == nullptr) return -1;
   if ((((uintptr_t)w2) & 15) || (((uintptr_t)a1) & 15) || (((uintptr_t)idx1) & 15) || (((uintptr_t)a2) & 7) ||
       (((uintptr_t)idx2) & 1))
@@ -2721,7 +2729,7 @@ static int fc1_bwd_launch(const Fc1Bwd& a, void* stream) {
   int nst = 0;
   if (a.stage_x != nullptr) {
     if (a.nsrc.perm == nullptr || a.nsrc.cursor == nullptr || a.nsrc.labels == nullptr || !a.nsrc.is_u8 ||
-        a.stage_lab == nullptr || a.stage_tag == nullptr || a.nsrc.n_total <= 0 ||
+        a.stage_lab == nullptr || a.stage_tag == nullptr || a.nsrc.n_total <= 0 || B > a.nsrc.n_total ||
         ((((uintptr_t)a.nsrc.x) | ((uintptr_t)a.stage_x)) & 15))
       return -1;
     nst = (B + 3) / 4;
@@ -2982,7 +2990,7 @@ int pto_mnist_fc1_bwd_head(const float* hp0, const float* hp1, const float* w2, 
   int nst = 0;
   if (stage_x != nullptr) {
     if (nperm == nullptr || ncursor == nullptr || nlabels == nullptr || stage_lab == nullptr || stage_tag == nullptr ||
-        n_total <= 0 || ((((uintptr_t)nx) | ((uintptr_t)stage_x)) & 15))
+        n_total <= 0 || B > n_total || ((((uintptr_t)nx) | ((uintptr_t)stage_x)) & 15))
       return -1;
     a.nsrc = make_src(nx, 1, nlabels, nperm, ncursor, 0, n_total, 1.f, 0.f);
     a.stage_adv = stage_adv;

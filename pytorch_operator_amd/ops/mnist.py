@@ -48,7 +48,8 @@ class BatchSource:
     ``perm``: optional int32 [N] order; the batch is ``perm[offset : offset+B]``
     (wrapping), with ``offset = cursor[0]*B % N`` when a device ``cursor`` is given
     (graph replay) or ``host_offset`` otherwise.  Without ``perm`` the batch is
-    rows ``0..B-1`` of ``x``.
+    rows ``0..B-1`` of ``x``.  A batch wraps at most once: ``check_batch`` rejects
+    ``B > N`` and a ``host_offset`` outside ``[0, N)``.
     """
 
     def __init__(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None,
@@ -85,8 +86,12 @@ class BatchSource:
         self.host_offset = int(host_offset)
 
     def check_batch(self, B: int) -> None:
-        if self.perm is None and B > self.n_total:
+        # the kernels' row functions (batch_row, batch_row_at) wrap at most once past the end of
+        # the permutation: a larger batch, or an offset outside it, would read out of bounds
+        if B > self.n_total:
             raise ValueError(f"batch {B} larger than dataset {self.n_total}")
+        if not 0 <= self.host_offset < self.n_total:
+            raise ValueError(f"host_offset {self.host_offset} outside [0, {self.n_total})")
 
 
 def conv1_fwd(src: BatchSource, w: torch.Tensor, b: torch.Tensor, B: int,
@@ -360,6 +365,7 @@ def fc1_bwd(dh, a2, idx2, w1, dlogits, h, gw1, gb1, gw2, gb2, dz2=None, per_samp
             raise ValueError("staging needs jobs DGRAD|FC2 (+WGRAD) and a uint8 BatchSource with labels, perm, cursor")
         if stage.B < B or src.x.data_ptr() % 16:
             raise ValueError("stage too small or unaligned source")
+        src.check_batch(B)
         rc = lib.pto_mnist_fc1_bwd_stage(
             dh.data_ptr(), a2.data_ptr(), idx2.data_ptr(), w1.data_ptr(), dlogits.data_ptr(), h.data_ptr(),
             gw1.data_ptr(), gb1.data_ptr(), gw2.data_ptr(), gb2.data_ptr(), _ptr(dz2), _ptr(per_sample),
@@ -424,6 +430,7 @@ def fc1_bwd_head(h_parts, w2, b2, lab, a2, idx2, w1, *, dz2, h_out, dh_out, dlog
     if stage is not None:
         if src is None or not BatchStage.supported(src) or stage.B < B or src.x.data_ptr() % 16:
             raise ValueError("staging needs a uint8 BatchSource with labels, perm, cursor and a large enough stage")
+        src.check_batch(B)
         st = (src.x.data_ptr(), src.labels.data_ptr(), src.perm.data_ptr(), src.cursor.data_ptr(), src.n_total,
               int(stage_adv), stage.x.data_ptr(), stage.lab.data_ptr(), stage.tag.data_ptr())
     rc = lib.pto_mnist_fc1_bwd_head(h_parts[0].data_ptr(), h_parts[1].data_ptr(), w2.data_ptr(),
