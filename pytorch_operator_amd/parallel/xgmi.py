@@ -91,10 +91,13 @@ class XgmiAllReduce:
         handle = ctypes.create_string_buffer(64)
         rc = self.lib.pto_xar_create(self.rank, self.world, self.n, nblk, timeout_s,
                                      ctypes.byref(self._ctx), handle)
-        handles = [None] * self.world
-        dist.all_gather_object(handles, handle.raw if rc == 0 else b"", group=group)
-        if rc != 0 or any(len(h) != 64 for h in handles):
+        created = [None] * self.world
+        dist.all_gather_object(created, (rc, handle.raw if rc == 0 else b""), group=group)
+        rcs, handles = [r for r, _ in created], [h for _, h in created]
+        if any(rcs) or any(len(h) != 64 for h in handles):
             self._ctx = None
+            if -3 in rcs:  # the export itself: e.g. ranks in pod-private PID namespaces (docs/xgmi_pods.md)
+                raise XgmiUnavailable(f"hipIpcGetMemHandle failed: {rcs}")
             raise XgmiUnavailable(f"pto_xar_create failed on some rank (local rc={rc})")
         blob = b"".join(handles)
         rc = self.lib.pto_xar_open(self._ctx, blob)

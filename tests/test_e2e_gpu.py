@@ -55,9 +55,13 @@ def test_gpu_mnist_job_hip_kernels(tmp_path):
 def test_two_pod_xgmi_job_needs_the_pod_topology(tmp_path, topology):
     """Two one-GPU pods of one job exchanging gradients over peer memory (the xGMI kernel;
     gloo carries only the rendezvous because both pods share this box's single GPU).
-    With the kubelet giving pods their own PID/IPC namespaces, the peer-memory IPC import
+    With the kubelet giving pods their own PID/IPC namespaces, the peer-memory IPC exchange
     must FAIL unless the operator's --xgmi-pod-topology put the pods in the node's
-    namespaces (docs/xgmi_pods.md) -- then the job succeeds on the xGMI path."""
+    namespaces (docs/xgmi_pods.md) -- then the job succeeds on the xGMI path.
+    The isolated job fails in one of the two IPC calls: the import (hipIpcOpenMemHandle) cannot
+    reach an exporter in another PID namespace; and where the pods' workers are each PID 1 of
+    their own PID namespace but share the emulator's network namespace, the dmabuf export
+    (hipIpcGetMemHandle) of the second pod to ask already fails (seen on ROCm 7.2)."""
     from pytorch_operator_amd.cluster.kubelet import namespaces_available
     ok, why = namespaces_available()
     if not ok and not topology:
@@ -91,4 +95,6 @@ def test_two_pod_xgmi_job_needs_the_pod_topology(tmp_path, topology):
         else:
             assert not pod["spec"].get("hostPID")
             assert types[-1] == "Failed", blob
-            assert "hipIpcOpenMemHandle failed" in blob, blob
+            assert "hipIpcOpenMemHandle failed" in blob or "hipIpcGetMemHandle failed" in blob, blob
+            for v in logs.values():
+                assert '"path": "xgmi"' not in v

@@ -134,11 +134,18 @@ def test_resnet50_train_mode_batchnorm_matches_fp64_like_cpu_fp32(full_fp32_conv
 
 def test_resnet50_bf16_sgd_fits_a_fixed_batch(algo_search):
     """The worker's optimizer (fused SGD, momentum 0.9, wd 1e-4) under bf16 autocast drives the
-    loss of one fixed 16-image batch well below chance."""
+    loss of one fixed 16-image batch well below chance.
+
+    The learning rate keeps the fit in the stable regime, where the loss falls from the first
+    step on and repeated runs end within ~10 % of each other (0.004-0.006 after 30 steps).  At
+    lr = 0.02 this net (randomised BN weights, no zero-init residual branches) first diverges
+    -- the loss climbs from 2.4 to 10-16 within six steps -- and how soon it recovers is decided
+    by the run-to-run rounding noise of the library's convolution gradients: ten runs of the
+    same code ended between 0.002 and 0.28, and one still at 2.46, above the bound below."""
     net = _net(seed=5).cuda().to(memory_format=torch.channels_last)
     x, y = _batch(B=16, seed=7)
     x, y = x.cuda().to(memory_format=torch.channels_last), y.cuda()
-    opt = torch.optim.SGD(net.parameters(), lr=0.02, momentum=0.9, weight_decay=1e-4, fused=True)
+    opt = torch.optim.SGD(net.parameters(), lr=0.005, momentum=0.9, weight_decay=1e-4, fused=True)
     losses = []
     for _ in range(30):
         opt.zero_grad(set_to_none=True)
