@@ -186,6 +186,9 @@ def parse_args(argv=None):
                    help="--sample-every: length of the default prompt (not with --sample-prompt)")
     p.add_argument("--sample-temperature", type=float, default=0.0, help="--sample-every: 0 = greedy")
     p.add_argument("--sample-top-k", type=int, default=0, help="--sample-every: 0 = the whole vocabulary")
+    p.add_argument("--decode-linear", choices=["lib", "hip"], default="lib",
+                   help="--sample-every: the decode step's projections and lm-head by the library GEMM, or by the "
+                        "skinny HIP GEMM (csrc/kernels/skinny_gemm.hip) where the worker's weights are bf16")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
@@ -194,7 +197,8 @@ def parse_args(argv=None):
                                   ("--sample-prompt", args.sample_prompt, None),
                                   ("--sample-prompt-len", args.sample_prompt_len, 16),
                                   ("--sample-temperature", args.sample_temperature, 0.0),
-                                  ("--sample-top-k", args.sample_top_k, 0)) if v != d]
+                                  ("--sample-top-k", args.sample_top_k, 0),
+                                  ("--decode-linear", args.decode_linear, "lib")) if v != d]
     if sampling and not args.model.startswith("llama"):
         p.error(f"{sampling[0]} is for the Llama models")
     args.sample_prompt_ids = None
@@ -617,10 +621,15 @@ def main(argv=None) -> int:
     def sample():
         """Continue the prompt (Llama.generate); touches neither the data generator, the feeds, the
         optimizer nor the gradients.  The KV cache lives for the call."""
-        with amp:
-            toks = bare.generate(torch.tensor([prompt_ids], dtype=torch.long, device=dev),
-                                 max_new_tokens=args.sample_tokens, temperature=args.sample_temperature,
-                                 top_k=args.sample_top_k, generator=sample_gen)
+        from ..models.llama import TNLinear
+        was, TNLinear.rows_impl = TNLinear.rows_impl, args.decode_linear
+        try:
+            with amp:
+                toks = bare.generate(torch.tensor([prompt_ids], dtype=torch.long, device=dev),
+                                     max_new_tokens=args.sample_tokens, temperature=args.sample_temperature,
+                                     top_k=args.sample_top_k, generator=sample_gen)
+        finally:
+            TNLinear.rows_impl = was
         if rank == 0:
             print(json.dumps({"event": "sample", "step": gstep, "prompt": prompt_ids, "tokens": toks[0].tolist()}),
                   flush=True)

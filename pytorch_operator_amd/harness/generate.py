@@ -29,6 +29,9 @@ def parse_args(argv=None):
                    help="as the worker's: bf16 autocast around the model (a GPU always runs bf16 projections)")
     p.add_argument("--attn", choices=["auto", "sdpa"], default="auto",
                    help="HIP prefill and decode attention where they apply, or the library's")
+    p.add_argument("--decode-linear", choices=["lib", "hip"], default="lib",
+                   help="the decode step's projections and lm-head: the library GEMM, or the skinny HIP GEMM "
+                        "(csrc/kernels/skinny_gemm.hip; the nn.Linear weights are cast to bf16 once after loading)")
     p.add_argument("--no-cuda", action="store_true")
     return p.parse_args(argv)
 
@@ -36,7 +39,7 @@ def parse_args(argv=None):
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
-    from ..models.llama import CONFIGS, Attention, Llama
+    from ..models.llama import CONFIGS, Attention, Llama, TNLinear
     from ..utils import train_ckpt
     from .ddp_train import parse_prompt
     cfg = CONFIGS[args.model]
@@ -47,6 +50,12 @@ def main(argv=None) -> int:
         with torch.device(dev):
             model = Llama(cfg)
         step = train_ckpt.load_weights(args.ckpt_dir, model, dev)
+        TNLinear.rows_impl = args.decode_linear
+        if args.decode_linear == "hip" and dev.type == "cuda":
+            # once, here: the kernel takes bf16 weights as they lie, and a cast per call would cost more than it
+            for mod in model.modules():
+                if isinstance(mod, torch.nn.Linear):
+                    mod.weight.data = mod.weight.data.to(torch.bfloat16)
         gen = torch.Generator(device=dev).manual_seed(args.seed) if args.temperature > 0 else None
         with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=args.dtype == "bf16"):
             toks = model.generate(torch.tensor([prompt], dtype=torch.long, device=dev), max_new_tokens=args.tokens,

@@ -119,11 +119,19 @@ class TNLinear(nn.Linear):
 
     impl = "tn"
     fp8_grad_format = "e5m2"  # impl "fp8": the output gradient's format (x and w are e4m3)
+    # calls with at most ops.skinny.MAX_ROWS rows (a decode step's): "hip" sends them to the skinny
+    # GEMM (ops.skinny.linear_rows) where rows_linear() allows, "lib" leaves every call where it was
+    rows_impl = "lib"
+    rows_calls = collections.Counter()  # such calls per path ("hip", "lib") on a GPU, as Attention.decode_calls
 
     def __init__(self, fin: int, fout: int):
         super().__init__(fin, fout, bias=False)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.is_cuda:
+            y = rows_linear(x, self.weight)
+            if y is not None:
+                return y
         if self.impl == "fp8":
             from ..ops import fp8
             return fp8.fp8_linear(x, self.weight, self.fp8_grad_format)
@@ -131,6 +139,29 @@ class TNLinear(nn.Linear):
             from ..ops.llm import linear_tn
             return linear_tn(x, self.weight)
         return super().forward(x)
+
+
+def rows_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, count_lib: bool = True):
+    """The decode step's choice for one CUDA projection.  A call of at most ``ops.skinny.MAX_ROWS`` rows
+    is counted in ``TNLinear.rows_calls``.  It goes to the skinny HIP GEMM (``ops.skinny.linear_rows``),
+    and its result is returned, when ``TNLinear.rows_impl == "hip"``, gradients are off, the input is
+    bf16 (or bf16 autocast is on), the weight is bf16 already (casting an fp32 weight per call costs more
+    than the GEMM: that case stays where it was) and the shape is inside ``ops.skinny.hip_supported``.
+    Otherwise None: the caller runs the path it always ran.  ``count_lib=False``: that path counts itself."""
+    from ..ops import skinny
+    if x.numel() > skinny.max_rows() * x.shape[-1]:
+        return None
+    hip = (TNLinear.rows_impl == "hip" and not torch.is_grad_enabled() and w.dtype == torch.bfloat16 and
+           (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled("cuda") and
+                                          torch.get_autocast_dtype("cuda") == torch.bfloat16)))
+    if hip:
+        x = x.to(torch.bfloat16)
+        hip = skinny.hip_supported(x, w, swiglu)
+    if not hip:
+        TNLinear.rows_calls["lib"] += int(count_lib)
+        return None
+    TNLinear.rows_calls["hip"] += 1
+    return skinny.linear_rows(x, w, swiglu)
 
 
 class LayerCache(NamedTuple):
@@ -206,6 +237,10 @@ class FeedForward(nn.Module):
 
     def forward(self, x):
         from ..ops.llm import swiglu_packed
+        if x.is_cuda and TNLinear.rows_impl == "hip":  # a decode step: the projection and SwiGLU in one launch
+            y = rows_linear(x, self.w13.weight, swiglu=True, count_lib=False)
+            if y is not None:
+                return self.w2(y)
         return self.w2(swiglu_packed(self.w13(x)))
 
 
@@ -267,6 +302,12 @@ class Llama(nn.Module):
         return cross_entropy(logits.reshape(-1, logits.shape[-1]), targets.reshape(-1), overwrite_logits=True)
 
     # ------------------------------------------------------------------ generation (ops.decode)
+    def _lm_head(self, y: torch.Tensor) -> torch.Tensor:
+        """``self.output`` for the few rows of a decode step, by TNLinear's ``rows_impl`` choice (``output``
+        stays a plain ``nn.Linear``: the state-dict keys are the checkpoints')."""
+        out = rows_linear(y, self.output.weight) if y.is_cuda else None
+        return self.output(y) if out is None else out
+
     def _low_precision(self, device) -> bool:
         """The projections run in bf16: under autocast, or with bf16 matmul weights."""
         return torch.is_autocast_enabled(device.type) or self.layers[0].attention.wqkv.weight.dtype == torch.bfloat16
@@ -309,7 +350,7 @@ class Llama(nn.Module):
         for i, blk in enumerate(self.layers):
             h, d = blk(h, d, cos, sin, None, LayerCache(cache.k[i], cache.v[i], None, None, None))
         rows, last = torch.arange(B, device=tokens.device), prompt_lens.to(tokens.device).long() - 1
-        logits = self.output(self.norm.add_forward(h[rows, last].unsqueeze(1), d[rows, last].unsqueeze(1))[1])
+        logits = self._lm_head(self.norm.add_forward(h[rows, last].unsqueeze(1), d[rows, last].unsqueeze(1))[1])
         cache.lens = prompt_lens.to(device=tokens.device, dtype=torch.int32).clone()
         return logits[:, 0]
 
@@ -324,7 +365,7 @@ class Llama(nn.Module):
         h, d = self.tok_embeddings(tokens).unsqueeze(1), None
         for i, blk in enumerate(self.layers):
             h, d = blk(h, d, cos, sin, None, LayerCache(cache.k[i], cache.v[i], pos, lens, mk))
-        logits = self.output(self.norm.add_forward(h, d)[1])
+        logits = self._lm_head(self.norm.add_forward(h, d)[1])
         cache.lens = lens
         return logits[:, 0]
 

@@ -197,6 +197,8 @@ _SIGNATURES = {
     # decode_attention.hip
     "pto_rope_append": [_VP] * 7 + [_L, _I, _I, _I, _I, _I, _I, _VP],
     "pto_decode_attn": [_VP] * 8 + [_I] * 7 + [_VP],
+    # skinny_gemm.hip
+    "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     # adamw.hip
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
     "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
@@ -242,7 +244,8 @@ _SIGNATURES = {
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
              "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
-             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": []}
+             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": [],
+             "pto_skinny_max_rows": [], "pto_skinny_waves": [_I]}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

@@ -4,6 +4,8 @@
 usage: python tools/decode_bench.py [--batch 1,8] [--keys 512,2048,8192] [--head-dim 64,128] [--hq 32] [--hkv 8]
                                     [--reps 200] [--json-out F]
        python tools/decode_bench.py --e2e [--model llama3-1b,llama3-8b] [--batch 1,8] [--prompt 128] [--tokens 128]
+                                    [--decode-linear lib,hip]
+       python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200]
 
 Kernel mode: one ``decode_attention`` call per cache layer, ``--reps`` calls back to back between two
 device events, every row at the full length n.  The calls walk over enough layers that K + V of all
@@ -16,7 +18,14 @@ issues the calls, per call, taken before any wait: where it equals the device fi
 bound by the host issuing them, not by the kernels.
 
 --e2e: ``Llama.generate`` tokens/s (bf16 matmul weights, random init), HIP against SDPA decode attention,
-alternating, two runs each; the prefill runs the HIP flash attention both times.
+alternating, two runs each; the prefill runs the HIP flash attention both times.  With --decode-linear lib,hip
+the attention stays on the HIP kernels and the decode step's projections change sides instead (the library
+GEMMs + a SwiGLU launch against ``ops.skinny.linear_rows``), each run checked by ``TNLinear.rows_calls``.
+
+--linear: ``ops.skinny.linear_rows`` against ``F.linear`` (+ ``swiglu_packed`` for w13) on the same tensors, at
+the five projection shapes of llama3-8b and llama3-1b and M = --rows.  The calls cycle through enough copies
+of the weight to exceed 512 MiB, so every call streams its weight from HBM ("gbps" = bytes of W / time, "peak"
+= that over 8 TB/s); sides alternate, two runs each, with the host's issue time beside the device's as above.
 """
 import argparse
 import json
@@ -83,6 +92,90 @@ def kernel_bench(a):
     return out
 
 
+def linear_shapes():
+    """(model, projection, N, K, swiglu) of the decode step's five GEMMs per model."""
+    from pytorch_operator_amd.models.llama import CONFIGS
+    for name in ("llama3-8b", "llama3-1b"):
+        c = CONFIGS[name]
+        qkv = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim
+        yield from ((name, "wqkv", qkv, c.dim, False), (name, "wo", c.dim, c.dim, False),
+                    (name, "w13", 2 * c.ffn_hidden, c.dim, True), (name, "w2", c.dim, c.ffn_hidden, False),
+                    (name, "output", c.vocab_size, c.dim, False))
+
+
+def linear_bench(a):
+    from pytorch_operator_amd.ops import _native
+    from pytorch_operator_amd.ops.llm import swiglu_packed
+    from pytorch_operator_amd.ops.skinny import linear_rows
+    out = []
+    for name, proj, N, K, swiglu in linear_shapes():
+        wbytes = N * K * 2
+        copies = max(2, -(-(512 << 20) // wbytes))
+        ws = (torch.randn(copies, N, K, device="cuda") * 0.02).to(torch.bfloat16)
+        for M in a.rows:
+            x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            fns = {"hip": lambda i: linear_rows(x, ws[i], swiglu),
+                   "lib": (lambda i: swiglu_packed(F.linear(x, ws[i]))) if swiglu else (lambda i: F.linear(x, ws[i]))}
+            row = {"model": name, "proj": proj, "M": M, "N": N, "K": K, "swiglu": swiglu, "copies": copies,
+                   "footprint_mb": round(copies * wbytes / 1e6, 1), "waves": int(_native.load().pto_skinny_waves(K))}
+            with torch.no_grad():
+                for side in ("hip", "lib", "hip", "lib"):
+                    dev_us, host_us = timed(fns[side], copies, a.reps)
+                    row.setdefault(side + "_us", []).append(round(dev_us, 2))
+                    row.setdefault(side + "_host_us", []).append(round(host_us, 2))
+            for side in ("hip", "lib"):
+                row[side + "_gbps"] = round(wbytes / min(row[side + "_us"]) / 1e3, 1)
+                row[side + "_peak"] = round(row[side + "_gbps"] / 8000.0, 3)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+        del ws
+        torch.cuda.empty_cache()
+    return out
+
+
+def e2e_linear_bench(a):
+    """tokens/s of ``Llama.generate`` with the decode step's projections on each side of --decode-linear."""
+    from pytorch_operator_amd.models.llama import CONFIGS, Llama, TNLinear
+    from pytorch_operator_amd.ops.optim import to_bf16_matmul_weights
+    out = []
+    for name in a.model:
+        torch.manual_seed(0)
+        with torch.device("cuda"):
+            model = Llama(CONFIGS[name])
+        to_bf16_matmul_weights(model)
+        for p in model.parameters():
+            if hasattr(p, "_pto_master"):
+                del p._pto_master  # the fp32 copy an optimizer would take over: not needed here
+        L = model.cfg.n_layers
+        for B in a.batch:
+            prompts = torch.randint(0, model.cfg.vocab_size, (B, a.prompt), device="cuda")
+            row = {"model": name, "B": B, "prompt": a.prompt, "new_tokens": a.tokens}
+            for i, side in enumerate(["warm"] + a.decode_linear * 2):
+                TNLinear.rows_impl = a.decode_linear[0] if side == "warm" else side
+                TNLinear.rows_calls.clear()
+                try:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    toks = model.generate(prompts, max_new_tokens=a.tokens)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    want = TNLinear.rows_impl
+                finally:
+                    TNLinear.rows_impl = "lib"
+                # every projection of the decode steps and every lm-head call took the side it is reported under
+                # (hip: the fused w13 is one call; lib: w13 is one call as well, its SwiGLU a launch of its own)
+                assert dict(TNLinear.rows_calls) == {want: (a.tokens - 1) * (4 * L + 1) + 1}, TNLinear.rows_calls
+                if side != "warm":
+                    row.setdefault(side + "_tokens_per_s", []).append(round(B * a.tokens / dt, 1))
+                    row.setdefault(side + "_ms_per_token", []).append(round(dt / a.tokens * 1e3, 3))
+            assert toks.shape == (B, a.tokens)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+        del model
+        torch.cuda.empty_cache()
+    return out
+
+
 def e2e_bench(a):
     from pytorch_operator_amd.models.llama import CONFIGS, Attention, Llama
     from pytorch_operator_amd.ops.optim import to_bf16_matmul_weights
@@ -134,11 +227,22 @@ def main():
     p.add_argument("--model", type=lambda s: s.split(","), default=["llama3-1b", "llama3-8b"])
     p.add_argument("--prompt", type=int, default=128)
     p.add_argument("--tokens", type=int, default=128)
+    p.add_argument("--linear", action="store_true", help="the skinny GEMM against F.linear at the decode step's shapes")
+    p.add_argument("--rows", type=ints, default=[1, 8, 16], help="--linear: batch rows M")
+    p.add_argument("--decode-linear", type=lambda s: s.split(","), default=None,
+                   help="--e2e: the sides of the projection A/B, e.g. lib,hip (default: the attention A/B)")
     p.add_argument("--json-out", default=None)
     a = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: needs a GPU (a CPU timing says nothing about these kernels)")
-    res = {"e2e": e2e_bench(a)} if a.e2e else {"kernel": kernel_bench(a)}
+    if a.decode_linear and (not a.e2e or set(a.decode_linear) - {"lib", "hip"}):
+        p.error("--decode-linear takes lib and / or hip, with --e2e")
+    if a.linear:
+        res = {"linear": linear_bench(a)}
+    elif a.e2e:
+        res = {"e2e_linear": e2e_linear_bench(a)} if a.decode_linear else {"e2e": e2e_bench(a)}
+    else:
+        res = {"kernel": kernel_bench(a)}
     if a.json_out:
         Path(a.json_out).write_text(json.dumps(res, indent=1) + "\n")
 
