@@ -29,9 +29,13 @@ def parse_args(argv=None):
                    help="as the worker's: bf16 autocast around the model (a GPU always runs bf16 projections)")
     p.add_argument("--attn", choices=["auto", "sdpa"], default="auto",
                    help="HIP prefill and decode attention where they apply, or the library's")
-    p.add_argument("--decode-linear", choices=["lib", "hip"], default="lib",
+    p.add_argument("--decode-linear", choices=["lib", "hip", "hip-fp8"], default="lib",
                    help="the decode step's projections and lm-head: the library GEMM, or the skinny HIP GEMM "
-                        "(csrc/kernels/skinny_gemm.hip; the nn.Linear weights are cast to bf16 once after loading)")
+                        "(csrc/kernels/skinny_gemm.hip; the nn.Linear weights are cast to bf16 once after loading), "
+                        "or hip-fp8: the skinny HIP GEMM on e4m3 weights with a power-of-two scale per output row "
+                        "(csrc/kernels/skinny_gemm_fp8.hip; the weights are cast to bf16, quantised once and "
+                        "overwritten with their dequantised values, so the model that runs is the quantised one "
+                        "on both the prefill and the decode step)")
     p.add_argument("--no-cuda", action="store_true")
     return p.parse_args(argv)
 
@@ -51,11 +55,13 @@ def main(argv=None) -> int:
             model = Llama(cfg)
         step = train_ckpt.load_weights(args.ckpt_dir, model, dev)
         TNLinear.rows_impl = args.decode_linear
-        if args.decode_linear == "hip" and dev.type == "cuda":
+        if args.decode_linear != "lib" and dev.type == "cuda":
             # once, here: the kernel takes bf16 weights as they lie, and a cast per call would cost more than it
             for mod in model.modules():
                 if isinstance(mod, torch.nn.Linear):
                     mod.weight.data = mod.weight.data.to(torch.bfloat16)
+            if args.decode_linear == "hip-fp8":
+                model.quantize_decode_weights(snap=True)
         gen = torch.Generator(device=dev).manual_seed(args.seed) if args.temperature > 0 else None
         with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=args.dtype == "bf16"):
             toks = model.generate(torch.tensor([prompt], dtype=torch.long, device=dev), max_new_tokens=args.tokens,

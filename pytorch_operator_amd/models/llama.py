@@ -120,16 +120,18 @@ class TNLinear(nn.Linear):
     impl = "tn"
     fp8_grad_format = "e5m2"  # impl "fp8": the output gradient's format (x and w are e4m3)
     # calls with at most ops.skinny.MAX_ROWS rows (a decode step's): "hip" sends them to the skinny
-    # GEMM (ops.skinny.linear_rows) where rows_linear() allows, "lib" leaves every call where it was
+    # GEMM (ops.skinny.linear_rows) where rows_linear() allows, "hip-fp8" to the one on e4m3 weights
+    # (ops.skinny.linear_rows_fp8) for the modules Llama.quantize_decode_weights() has prepared, "lib"
+    # leaves every call where it was
     rows_impl = "lib"
-    rows_calls = collections.Counter()  # such calls per path ("hip", "lib") on a GPU, as Attention.decode_calls
+    rows_calls = collections.Counter()  # such calls per path ("hip", "hip-fp8", "lib") on a GPU
 
     def __init__(self, fin: int, fout: int):
         super().__init__(fin, fout, bias=False)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
-            y = rows_linear(x, self.weight)
+            y = rows_linear(x, self.weight, mod=self)
             if y is not None:
                 return y
         if self.impl == "fp8":
@@ -141,27 +143,40 @@ class TNLinear(nn.Linear):
         return super().forward(x)
 
 
-def rows_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, count_lib: bool = True):
+def rows_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, count_lib: bool = True, mod=None):
     """The decode step's choice for one CUDA projection.  A call of at most ``ops.skinny.MAX_ROWS`` rows
     is counted in ``TNLinear.rows_calls``.  It goes to the skinny HIP GEMM (``ops.skinny.linear_rows``),
     and its result is returned, when ``TNLinear.rows_impl == "hip"``, gradients are off, the input is
     bf16 (or bf16 autocast is on), the weight is bf16 already (casting an fp32 weight per call costs more
     than the GEMM: that case stays where it was) and the shape is inside ``ops.skinny.hip_supported``.
+    With ``rows_impl == "hip-fp8"`` it goes to ``ops.skinny.linear_rows_fp8`` under the same conditions on
+    ``x``, when ``mod`` (the module that owns ``w``) carries the ``rows_q`` and ``rows_scale`` of
+    ``Llama.quantize_decode_weights`` and the shape is inside ``ops.skinny.hip_supported_fp8``.
     Otherwise None: the caller runs the path it always ran.  ``count_lib=False``: that path counts itself."""
     from ..ops import skinny
     if x.numel() > skinny.max_rows() * x.shape[-1]:
         return None
-    hip = (TNLinear.rows_impl == "hip" and not torch.is_grad_enabled() and w.dtype == torch.bfloat16 and
+    impl = TNLinear.rows_impl
+    hip = (impl in ("hip", "hip-fp8") and not torch.is_grad_enabled() and
            (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled("cuda") and
                                           torch.get_autocast_dtype("cuda") == torch.bfloat16)))
-    if hip:
+    if hip and impl == "hip":
         x = x.to(torch.bfloat16)
-        hip = skinny.hip_supported(x, w, swiglu)
+        hip = w.dtype == torch.bfloat16 and skinny.hip_supported(x, w, swiglu)
+    elif hip:
+        hip = getattr(mod, "rows_q", None) is not None
+        if hip:
+            if mod.rows_q.device != x.device:  # plain attributes do not follow Module.to(): once, here
+                mod.rows_q, mod.rows_scale = mod.rows_q.to(x.device), mod.rows_scale.to(x.device)
+            x = x.to(torch.bfloat16)
+            hip = skinny.hip_supported_fp8(x, mod.rows_q, mod.rows_scale, swiglu)
     if not hip:
         TNLinear.rows_calls["lib"] += int(count_lib)
         return None
-    TNLinear.rows_calls["hip"] += 1
-    return skinny.linear_rows(x, w, swiglu)
+    TNLinear.rows_calls[impl] += 1
+    if impl == "hip":
+        return skinny.linear_rows(x, w, swiglu)
+    return skinny.launch_rows_fp8(x, mod.rows_q, mod.rows_scale, swiglu)
 
 
 class LayerCache(NamedTuple):
@@ -237,8 +252,9 @@ class FeedForward(nn.Module):
 
     def forward(self, x):
         from ..ops.llm import swiglu_packed
-        if x.is_cuda and TNLinear.rows_impl == "hip":  # a decode step: the projection and SwiGLU in one launch
-            y = rows_linear(x, self.w13.weight, swiglu=True, count_lib=False)
+        # a decode step: the projection and SwiGLU in one launch
+        if x.is_cuda and TNLinear.rows_impl in ("hip", "hip-fp8"):
+            y = rows_linear(x, self.w13.weight, swiglu=True, count_lib=False, mod=self.w13)
             if y is not None:
                 return self.w2(y)
         return self.w2(swiglu_packed(self.w13(x)))
@@ -305,8 +321,24 @@ class Llama(nn.Module):
     def _lm_head(self, y: torch.Tensor) -> torch.Tensor:
         """``self.output`` for the few rows of a decode step, by TNLinear's ``rows_impl`` choice (``output``
         stays a plain ``nn.Linear``: the state-dict keys are the checkpoints')."""
-        out = rows_linear(y, self.output.weight) if y.is_cuda else None
+        out = rows_linear(y, self.output.weight, mod=self.output) if y.is_cuda else None
         return self.output(y) if out is None else out
+
+    @torch.no_grad()
+    def quantize_decode_weights(self, snap: bool = True) -> int:
+        """Prepare ``TNLinear.rows_impl = "hip-fp8"``: every ``TNLinear`` and ``output`` gets ``rows_q`` (e4m3
+        [N, K]) and ``rows_scale`` (fp32 [N], powers of two) of ``ops.skinny.quantize_rows`` as plain
+        attributes -- neither parameters nor buffers, so state-dict keys and checkpoints do not change.
+        ``snap``: the weight itself is overwritten in place with the dequantised value (exact in bf16), so
+        the prefill (library GEMM on the weight) and the decode step (the kernel on ``rows_q``) run the same
+        model.  The weights are kept: memory goes up by a byte per weight.  Returns the number of modules."""
+        from ..ops.skinny import dequantize_rows, quantize_rows
+        mods = [m for m in self.modules() if isinstance(m, TNLinear)] + [self.output]
+        for m in mods:
+            m.rows_q, m.rows_scale = quantize_rows(m.weight)
+            if snap:
+                m.weight.copy_(dequantize_rows(m.rows_q, m.rows_scale, m.weight.dtype))
+        return len(mods)
 
     def _low_precision(self, device) -> bool:
         """The projections run in bf16: under autocast, or with bf16 matmul weights."""

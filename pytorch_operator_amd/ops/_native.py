@@ -53,6 +53,9 @@ def _sources():
 # own asm MFMAs, so the compiler's MFMAs (S, dP) write VGPRs that the VALU reads directly), and
 # no SLP vectorisation: packed f32 VALU beside MFMAs costs more issue time than two scalar ops
 # (MI355X_MICROARCH.md, constants table).
+# skinny_gemm_fp8.hip: no packed fp32 VALU ops (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): its reduce and
+# its scale multiply are fp32 vectors the compiler would pack, and the kernel's bit-identity claims rest on
+# plain fp32 arithmetic.
 # mnist_kernels.hip: kernel-argument preloading -- the command processor writes the leading 14
 # argument dwords into user SGPRs at wave launch, so the step kernels (whose parameter lists lead
 # with what their first loads need) start without a scalar-load round trip; firmware without the
@@ -60,7 +63,8 @@ def _sources():
 _FILE_FLAGS = {"mnist_kernels.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
                "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_d64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
+               "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
+               "skinny_gemm_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _source_digest() -> str:
@@ -199,6 +203,8 @@ _SIGNATURES = {
     "pto_decode_attn": [_VP] * 8 + [_I] * 7 + [_VP],
     # skinny_gemm.hip
     "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
+    # skinny_gemm_fp8.hip
+    "pto_skinny_fp8_gemm": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP],
     # adamw.hip
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
     "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
@@ -245,7 +251,8 @@ _SIGNATURES = {
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
              "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
              "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": [],
-             "pto_skinny_max_rows": [], "pto_skinny_waves": [_I]}
+             "pto_skinny_max_rows": [], "pto_skinny_waves": [_I],
+             "pto_skinny_fp8_waves": [_I], "pto_skinny_fp8_tiles": [_I, _I, _I]}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

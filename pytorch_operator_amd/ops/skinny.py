@@ -7,6 +7,9 @@ accumulation; with ``swiglu``, ``w`` is the packed [W1 | W3] of ``FeedForward.w1
 ``swiglu_packed(F.linear(x, w))`` [..., N / 2] from one launch, bit for bit what the two launches give.
 Inference only.  On a GPU the HIP kernel runs, and a shape or dtype outside its contract
 (``hip_supported``) is a ``ValueError``, never a silent fallback; on CPU the same math runs in PyTorch.
+
+``quantize_rows`` / ``linear_rows_fp8(x, q, scale, swiglu=False, tiles=0)``: the same on e4m3 weights with a
+power-of-two scale per output row (``csrc/kernels/skinny_gemm_fp8.hip``), under the same rules; see below.
 """
 from __future__ import annotations
 
@@ -73,4 +76,91 @@ def linear_rows(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False) -> torch
     y = x.new_empty(*x.shape[:-1], N // 2 if swiglu else N)
     _native.check(_native.load().pto_skinny_gemm(x2.data_ptr(), w.data_ptr(), y.data_ptr(), x2.shape[0], N, K,
                                                  int(swiglu), _stream(x)), "skinny_gemm")
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------------
+# FP8 weights (``csrc/kernels/skinny_gemm_fp8.hip``): OCP e4m3 with one power-of-two scale per output row,
+# bf16 activations, fp32 accumulation -- half the weight bytes of a decode step.  e4m3 -> bf16 is exact and
+# so is the multiply by a power of two: ``dequantize_rows(q, scale)`` is a bf16 matrix, and
+# ``linear_rows_fp8(x, q, scale)`` is ``linear_rows`` on it.
+
+E4M3_MAX = 448.0
+FP8_TILES = (0, 1, 2, 4)  # accumulators per wave a caller may force; 0: the library picks from (M, N)
+
+
+def quantize_rows(w: torch.Tensor):
+    """``w`` [N, K] -> (``q`` e4m3 [N, K] contiguous, ``scale`` fp32 [N]) with ``scale[n] =
+    2^ceil(log2(amax_n / 448))`` (1 for a zero row) and ``q = w / scale`` rounded to e4m3: the quotient is
+    inside +-448 by construction, and the largest of a row lands in (224, 448]."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_rows: w [N, K]; got {tuple(w.shape)}")
+    amax = w.detach().abs().amax(dim=1).double()
+    m, e = torch.frexp(amax / E4M3_MAX)               # amax / 448 = m 2^e, m in [0.5, 1)
+    e = torch.where(m == 0.5, e - 1, e)               # ceil(log2(.)): e, but e - 1 at an exact power of two
+    scale = torch.ldexp(torch.ones_like(amax), e.clamp(-126, 127)).float()
+    scale = torch.where(amax > 0, scale, torch.ones_like(scale))
+    q = (w.detach().float() / scale[:, None]).to(torch.float8_e4m3fn).contiguous()
+    return q, scale
+
+
+def dequantize_rows(q: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """``scale[:, None] * q`` in ``dtype``: exact in bf16 (and anything wider) for a power-of-two scale."""
+    return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+def _fp8_contract(x, q, scale, swiglu, tiles) -> bool:
+    """What both devices ask: shapes, dtypes of q and scale, tiles."""
+    if q.dim() != 2 or x.dim() < 1 or x.shape[-1] != q.shape[1] or scale.shape != (q.shape[0],):
+        return False
+    if q.dtype != torch.float8_e4m3fn or scale.dtype != torch.float32 or tiles not in FP8_TILES:
+        return False
+    N, K = q.shape
+    return (1 <= _rows(x) <= max_rows() and N > 0 and N % (32 if swiglu else 16) == 0 and K % 64 == 0
+            and q.is_contiguous() and scale.is_contiguous())
+
+
+def hip_supported_fp8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+                      tiles: int = 0) -> bool:
+    """The kernel's contract: bf16 CUDA ``x``, 1..MAX_ROWS rows; ``q`` e4m3 [N, K], contiguous and 16-byte
+    aligned; ``scale`` fp32 [N]; N % 16 == 0 (N % 32 == 0 with ``swiglu``), K % 64 == 0; ``tiles`` in
+    ``FP8_TILES``; no gradient asked for."""
+    if not (x.is_cuda and q.is_cuda and scale.is_cuda) or x.dtype != torch.bfloat16:
+        return False
+    if torch.is_grad_enabled() and x.requires_grad:
+        return False
+    return _fp8_contract(x, q, scale, swiglu, tiles) and q.data_ptr() % 16 == 0
+
+
+def linear_rows_fp8_reference(x, q, scale, swiglu: bool = False) -> torch.Tensor:
+    y = F.linear(x, dequantize_rows(q, scale, x.dtype))
+    return swiglu_packed_reference(y) if swiglu else y
+
+
+def linear_rows_fp8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+                    tiles: int = 0) -> torch.Tensor:
+    """``linear_rows(x, dequantize_rows(q, scale), swiglu)`` from the e4m3 bytes.  ``tiles`` forces the
+    accumulators per wave (tests, benchmarks); the result does not depend on it."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise ValueError("linear_rows_fp8: inference only (no backward); call it under torch.no_grad()")
+    ok = hip_supported_fp8(x, q, scale, swiglu, tiles) if x.is_cuda else _fp8_contract(x, q, scale, swiglu, tiles)
+    if not ok:
+        raise ValueError(f"linear_rows_fp8: x [..., K] of 1 to {max_rows()} rows (bf16 on a GPU), q [N, K] e4m3, "
+                         f"contiguous and 16-byte aligned, scale [N] fp32, N % {32 if swiglu else 16} == 0, "
+                         f"K % 64 == 0, tiles in {FP8_TILES}; got x {tuple(x.shape)} {x.dtype}, q {tuple(q.shape)} "
+                         f"{q.dtype} stride {q.stride()}, scale {tuple(scale.shape)} {scale.dtype}, tiles {tiles}")
+    if not x.is_cuda:
+        return linear_rows_fp8_reference(x, q, scale, swiglu)
+    return launch_rows_fp8(x, q, scale, swiglu, tiles)
+
+
+def launch_rows_fp8(x, q, scale, swiglu: bool = False, tiles: int = 0) -> torch.Tensor:
+    """The launch alone, for a caller that has just asked ``hip_supported_fp8`` about these very arguments
+    (``models.llama.rows_linear``: a decode step is bound by the host, and the checks are most of a call)."""
+    N, K = q.shape
+    x2 = _aligned(x.reshape(-1, K))
+    y = x.new_empty(*x.shape[:-1], N // 2 if swiglu else N)
+    _native.check(_native.load().pto_skinny_fp8_gemm(x2.data_ptr(), q.data_ptr(), scale.data_ptr(), y.data_ptr(),
+                                                     x2.shape[0], N, K, int(swiglu), tiles, _stream(x)),
+                  "skinny_fp8_gemm")
     return y

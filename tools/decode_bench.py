@@ -4,8 +4,9 @@
 usage: python tools/decode_bench.py [--batch 1,8] [--keys 512,2048,8192] [--head-dim 64,128] [--hq 32] [--hkv 8]
                                     [--reps 200] [--json-out F]
        python tools/decode_bench.py --e2e [--model llama3-1b,llama3-8b] [--batch 1,8] [--prompt 128] [--tokens 128]
-                                    [--decode-linear lib,hip]
-       python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200]
+                                    [--decode-linear lib,hip,hip-fp8]
+       python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200] [--decode-linear hip-fp8,hip,lib]
+                                             [--fp8-tiles 1,2,4]
 
 Kernel mode: one ``decode_attention`` call per cache layer, ``--reps`` calls back to back between two
 device events, every row at the full length n.  The calls walk over enough layers that K + V of all
@@ -26,6 +27,10 @@ GEMMs + a SwiGLU launch against ``ops.skinny.linear_rows``), each run checked by
 the five projection shapes of llama3-8b and llama3-1b and M = --rows.  The calls cycle through enough copies
 of the weight to exceed 512 MiB, so every call streams its weight from HBM ("gbps" = bytes of W / time, "peak"
 = that over 8 TB/s); sides alternate, two runs each, with the host's issue time beside the device's as above.
+With hip-fp8 among --decode-linear, ``ops.skinny.linear_rows_fp8`` on ``quantize_rows`` of the same weights is a
+third side ("fp8": its "gbps" counts its own, one-byte weights), and the copies are sized so that the e4m3 ones
+alone exceed 512 MiB.  --fp8-tiles adds one side per forced accumulator count ("fp8_t1", ...), where "fp8" is the
+library's own choice ("tiles").
 """
 import argparse
 import json
@@ -106,25 +111,40 @@ def linear_shapes():
 def linear_bench(a):
     from pytorch_operator_amd.ops import _native
     from pytorch_operator_amd.ops.llm import swiglu_packed
-    from pytorch_operator_amd.ops.skinny import linear_rows
+    from pytorch_operator_amd.ops.skinny import linear_rows, linear_rows_fp8, quantize_rows
+    fp8 = "hip-fp8" in (a.decode_linear or [])
+    sides = [{"hip-fp8": "fp8"}.get(s, s) for s in (a.decode_linear or ["hip", "lib"])]
+    sides = sides[:1] + [f"fp8_t{t}" for t in a.fp8_tiles if fp8] + sides[1:]
+    lib = _native.load()
     out = []
     for name, proj, N, K, swiglu in linear_shapes():
         wbytes = N * K * 2
-        copies = max(2, -(-(512 << 20) // wbytes))
-        ws = (torch.randn(copies, N, K, device="cuda") * 0.02).to(torch.bfloat16)
+        copies = max(2, -(-(512 << 20) // (wbytes // 2 if fp8 else wbytes)))
+        ws = torch.empty(copies, N, K, dtype=torch.bfloat16, device="cuda")
+        for i in range(copies):  # a copy at a time: the fp32 draw of all of them would be 4 bytes a weight
+            ws[i] = torch.randn(N, K, device="cuda") * 0.02
+        if fp8:
+            qs = [quantize_rows(ws[i]) for i in range(copies)]
         for M in a.rows:
             x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
             fns = {"hip": lambda i: linear_rows(x, ws[i], swiglu),
-                   "lib": (lambda i: swiglu_packed(F.linear(x, ws[i]))) if swiglu else (lambda i: F.linear(x, ws[i]))}
+                   "lib": (lambda i: swiglu_packed(F.linear(x, ws[i]))) if swiglu else (lambda i: F.linear(x, ws[i])),
+                   "fp8": lambda i: linear_rows_fp8(x, *qs[i], swiglu)}
+            for t in a.fp8_tiles:
+                fns[f"fp8_t{t}"] = lambda i, t=t: linear_rows_fp8(x, *qs[i], swiglu, t)
             row = {"model": name, "proj": proj, "M": M, "N": N, "K": K, "swiglu": swiglu, "copies": copies,
-                   "footprint_mb": round(copies * wbytes / 1e6, 1), "waves": int(_native.load().pto_skinny_waves(K))}
+                   "footprint_mb": round(copies * wbytes / 1e6, 1), "waves": int(lib.pto_skinny_waves(K))}
+            if fp8:
+                row.update(fp8_footprint_mb=round(copies * wbytes / 2e6, 1),
+                           tiles=int(lib.pto_skinny_fp8_tiles(M, N, int(swiglu))))
             with torch.no_grad():
-                for side in ("hip", "lib", "hip", "lib"):
+                for side in sides * 2:
                     dev_us, host_us = timed(fns[side], copies, a.reps)
                     row.setdefault(side + "_us", []).append(round(dev_us, 2))
                     row.setdefault(side + "_host_us", []).append(round(host_us, 2))
-            for side in ("hip", "lib"):
-                row[side + "_gbps"] = round(wbytes / min(row[side + "_us"]) / 1e3, 1)
+            for side in sides:
+                own = wbytes // 2 if side.startswith("fp8") else wbytes
+                row[side + "_gbps"] = round(own / min(row[side + "_us"]) / 1e3, 1)
                 row[side + "_peak"] = round(row[side + "_gbps"] / 8000.0, 3)
             print(json.dumps(row), flush=True)
             out.append(row)
@@ -146,6 +166,8 @@ def e2e_linear_bench(a):
         for p in model.parameters():
             if hasattr(p, "_pto_master"):
                 del p._pto_master  # the fp32 copy an optimizer would take over: not needed here
+        if "hip-fp8" in a.decode_linear:
+            model.quantize_decode_weights(snap=True)  # every side then runs the same, quantised, model
         L = model.cfg.n_layers
         for B in a.batch:
             prompts = torch.randint(0, model.cfg.vocab_size, (B, a.prompt), device="cuda")
@@ -230,13 +252,17 @@ def main():
     p.add_argument("--linear", action="store_true", help="the skinny GEMM against F.linear at the decode step's shapes")
     p.add_argument("--rows", type=ints, default=[1, 8, 16], help="--linear: batch rows M")
     p.add_argument("--decode-linear", type=lambda s: s.split(","), default=None,
-                   help="--e2e: the sides of the projection A/B, e.g. lib,hip (default: the attention A/B)")
+                   help="--e2e: the sides of the projection A/B, e.g. lib,hip or lib,hip,hip-fp8 (default: the "
+                        "attention A/B); --linear: the sides in their order (default hip,lib)")
+    p.add_argument("--fp8-tiles", type=ints, default=[], help="--linear with hip-fp8: also each forced tile count")
     p.add_argument("--json-out", default=None)
     a = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: needs a GPU (a CPU timing says nothing about these kernels)")
-    if a.decode_linear and (not a.e2e or set(a.decode_linear) - {"lib", "hip"}):
-        p.error("--decode-linear takes lib and / or hip, with --e2e")
+    if a.decode_linear and (not (a.e2e or a.linear) or set(a.decode_linear) - {"lib", "hip", "hip-fp8"}):
+        p.error("--decode-linear takes lib, hip and / or hip-fp8, with --e2e or --linear")
+    if set(a.fp8_tiles) - {1, 2, 4}:
+        p.error("--fp8-tiles takes 1, 2 and / or 4")
     if a.linear:
         res = {"linear": linear_bench(a)}
     elif a.e2e:
