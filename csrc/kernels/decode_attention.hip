@@ -22,16 +22,10 @@
 //            ceil(n / kChunk) partials of a row in chunk order -- it reads lens itself, so partials
 //            that an earlier call left in the workspace beyond that count are never read.  No
 //            atomics anywhere: the same inputs and max_keys give the same bits.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "pto_vec.h"
+#include "decode_common.h"
 
 namespace {
 
-constexpr int kT = 256;
-constexpr int kChunk = 256;  // keys per workgroup
 constexpr int kU = 4;        // cache rows a lane has in flight (16-byte loads issued before the first use)
 
 using V8 = pto::Vec<8>;
@@ -252,42 +246,6 @@ __global__ __launch_bounds__(kT) void decode_attn_kernel(const uint16_t* __restr
     pl[pbase + (long)tid * nchunks + chunk] = stat[1][tid];
   }
 }
-
-// One workgroup of D threads per (batch row, query head): merge the row's valid partials in order.
-template <int D>
-__global__ __launch_bounds__(D) void decode_combine_kernel(const float* __restrict__ po,
-                                                           const float* __restrict__ pm,
-                                                           const float* __restrict__ pl,
-                                                           const int* __restrict__ lens, uint16_t* __restrict__ o,
-                                                           int max_keys, int Hq, int nchunks) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  int n = lens[b];
-  n = n < max_keys ? n : max_keys;
-  const long r = (long)b * Hq + h;
-  float out = 0.f;
-  if (n > 0) {
-    const int nc = (n + kChunk - 1) / kChunk;  // <= nchunks, as n <= max_keys
-    const float* m = pm + r * nchunks;
-    const float* l = pl + r * nchunks;
-    float M = m[0];
-    for (int c = 1; c < nc; ++c) M = fmaxf(M, m[c]);
-    float num = 0.f, den = 0.f;
-    for (int c = 0; c < nc; ++c) {
-      const float f = __expf(m[c] - M);
-      num = fmaf(f, po[(r * nchunks + c) * D + d], num);
-      den = fmaf(f, l[c], den);
-    }
-    out = num / den;
-  }
-  pto::store1(o + r * D + d, out);
-}
-
-unsigned grid_for(long work) {
-  const long b = (work + kT - 1) / kT;
-  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 template <int D, int G>
 void launch_decode(const void* q, const void* kc, const void* vc, const int* lens, float* po, float* pm, float* pl,

@@ -36,6 +36,10 @@ def parse_args(argv=None):
                         "(csrc/kernels/skinny_gemm_fp8.hip; the weights are cast to bf16, quantised once and "
                         "overwritten with their dequantised values, so the model that runs is the quantised one "
                         "on both the prefill and the decode step)")
+    p.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
+                   help="fp8: the KV cache in e4m3 with a power-of-two scale per (token, kv head), written and read "
+                        "by csrc/kernels/decode_attention_fp8.hip: half the cache bytes. It quantises k and v, so "
+                        "the logits, and with them the tokens, differ from the bf16 cache's")
     p.add_argument("--no-cuda", action="store_true")
     return p.parse_args(argv)
 
@@ -65,7 +69,8 @@ def main(argv=None) -> int:
         gen = torch.Generator(device=dev).manual_seed(args.seed) if args.temperature > 0 else None
         with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=args.dtype == "bf16"):
             toks = model.generate(torch.tensor([prompt], dtype=torch.long, device=dev), max_new_tokens=args.tokens,
-                                  temperature=args.temperature, top_k=args.top_k, eos_id=args.eos_id, generator=gen)
+                                  temperature=args.temperature, top_k=args.top_k, eos_id=args.eos_id, generator=gen,
+                                  kv_dtype=torch.float8_e4m3fn if args.kv_cache == "fp8" else None)
     except ValueError as e:
         print(f"error: {e}", file=sys.stderr, flush=True)
         return 2

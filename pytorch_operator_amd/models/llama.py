@@ -182,12 +182,15 @@ def rows_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, count_li
 class LayerCache(NamedTuple):
     """One layer's view of an ``ops.decode.KVCache`` for one forward: ``k``, ``v`` [B, max_len, Hkv, D];
     a decode step also needs ``pos`` (the row to append at), ``lens`` (valid rows after the append),
-    both int32 [B] on the device, and the host-known bound ``max_keys``.  A prefill leaves them None."""
+    both int32 [B] on the device, and the host-known bound ``max_keys``.  A prefill leaves them None.
+    ``k_scale``, ``v_scale`` [B, Hkv, max_len_pad]: the layer's scales when the cache is e4m3, else None."""
     k: torch.Tensor
     v: torch.Tensor
     pos: Optional[torch.Tensor]
     lens: Optional[torch.Tensor]
     max_keys: Optional[int]
+    k_scale: Optional[torch.Tensor] = None
+    v_scale: Optional[torch.Tensor] = None
 
 
 class Attention(nn.Module):
@@ -196,7 +199,8 @@ class Attention(nn.Module):
     head dim 64 or 128, ...), the library's ``scaled_dot_product_attention`` otherwise -- an fp32 model
     called without autocast, for instance, runs the library path on a GPU without an error (the
     ``ops`` wrappers themselves never fall back).  ``decode_calls`` counts the decode steps per path
-    ("hip", "sdpa", "cpu"), so that a benchmark or a test can assert which one it ran."""
+    ("hip", "hip-fp8" on an e4m3 cache, "sdpa", "cpu"), so that a benchmark or a test can assert which one
+    it ran."""
 
     impl = "auto"  # "auto": HIP flash attention where it applies; "sdpa": library kernels
     decode_impl = None  # the decode step alone: None follows impl; "sdpa" / "auto" for A/B runs (tools/decode_bench.py)
@@ -219,16 +223,24 @@ class Attention(nn.Module):
         from ..ops.llm import rope_qkv
         if cache is not None and S == 1:
             from ..ops import decode as Dc
-            q = Dc.rope_append(self.wqkv(x).reshape(B, -1), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv)
-            hip = (self.decode_impl or self.impl) != "sdpa" and (not q.is_cuda or Dc.hip_supported(q, cache.k, cache.v))
-            Attention.decode_calls["cpu" if not q.is_cuda else ("hip" if hip else "sdpa")] += 1
-            o = Dc.decode_attention(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa")
+            fp8 = cache.k.dtype == Dc.FP8  # the e4m3 cache has one path per device: no library side to fall to
+            q = Dc.rope_append(self.wqkv(x).reshape(B, -1), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv,
+                               cache.k_scale, cache.v_scale)
+            hip = fp8 or ((self.decode_impl or self.impl) != "sdpa"
+                          and (not q.is_cuda or Dc.hip_supported(q, cache.k, cache.v)))
+            Attention.decode_calls["cpu" if not q.is_cuda else (("hip-fp8" if fp8 else "hip") if hip else "sdpa")] += 1
+            o = Dc.decode_attention(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
+                                    cache.k_scale, cache.v_scale)
             return self.wo(o.reshape(B, 1, self.nh * self.hd))
         q, k, v = rope_qkv(self.wqkv(x), cos, sin, self.nh, self.nkv)
         if cache is not None:
             n = min(S, cache.k.shape[1])  # a prompt padded to the attention kernels' multiple may end past the cache
-            cache.k[:, :n].copy_(k[:, :n])
-            cache.v[:, :n].copy_(v[:, :n])
+            if cache.k_scale is not None:
+                from ..ops.decode import quantize_kv
+                quantize_kv(k, v, cache.k, cache.v, cache.k_scale, cache.v_scale)
+            else:
+                cache.k[:, :n].copy_(k[:, :n])
+                cache.v[:, :n].copy_(v[:, :n])
         if doc_start is not None:
             # packed documents: attention stays inside each one; RoPE positions stay absolute
             # (it is relative, so restarting them per document would change nothing)
@@ -346,12 +358,19 @@ class Llama(nn.Module):
 
     def new_cache(self, B: int, max_len: int, dtype=None):
         """An empty ``ops.decode.KVCache`` for ``B`` sequences of up to ``max_len`` tokens, in the dtype
-        the projections write (bf16 under autocast or with bf16 weights, else the weights' own)."""
+        the projections write (bf16 under autocast or with bf16 weights, else the weights' own), or in
+        ``dtype``: ``torch.float8_e4m3fn`` is the quantised cache of ``ops.decode``."""
         from ..ops.decode import KVCache
         w = self.layers[0].attention.wqkv.weight
         if dtype is None:
             dtype = torch.bfloat16 if self._low_precision(w.device) else w.dtype
         return KVCache(self.cfg.n_layers, B, max_len, self.cfg.n_kv_heads, self.cfg.head_dim, dtype, w.device)
+
+    @staticmethod
+    def _layer_cache(cache, i: int, pos=None, lens=None, max_keys=None) -> LayerCache:
+        if cache.k_scale is None:
+            return LayerCache(cache.k[i], cache.v[i], pos, lens, max_keys)
+        return LayerCache(cache.k[i], cache.v[i], pos, lens, max_keys, cache.k_scale[i], cache.v_scale[i])
 
     def _rope(self, cache, rows: int):
         if cache.rope is None or cache.rope[0].shape[0] < rows:
@@ -380,7 +399,7 @@ class Llama(nn.Module):
         cos, sin = cos[:S], sin[:S]
         h, d = self.tok_embeddings(tokens), None
         for i, blk in enumerate(self.layers):
-            h, d = blk(h, d, cos, sin, None, LayerCache(cache.k[i], cache.v[i], None, None, None))
+            h, d = blk(h, d, cos, sin, None, self._layer_cache(cache, i))
         rows, last = torch.arange(B, device=tokens.device), prompt_lens.to(tokens.device).long() - 1
         logits = self._lm_head(self.norm.add_forward(h[rows, last].unsqueeze(1), d[rows, last].unsqueeze(1))[1])
         cache.lens = prompt_lens.to(device=tokens.device, dtype=torch.int32).clone()
@@ -396,19 +415,20 @@ class Llama(nn.Module):
         cos, sin = self._rope(cache, cache.max_len)
         h, d = self.tok_embeddings(tokens).unsqueeze(1), None
         for i, blk in enumerate(self.layers):
-            h, d = blk(h, d, cos, sin, None, LayerCache(cache.k[i], cache.v[i], pos, lens, mk))
+            h, d = blk(h, d, cos, sin, None, self._layer_cache(cache, i, pos, lens, mk))
         logits = self._lm_head(self.norm.add_forward(h, d)[1])
         cache.lens = lens
         return logits[:, 0]
 
     def generate(self, prompts: torch.Tensor, prompt_lens=None, max_new_tokens: int = 32, temperature: float = 0.0,
                  top_k: int = 0, eos_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 return_logits: bool = False, max_len: Optional[int] = None):
+                 return_logits: bool = False, max_len: Optional[int] = None, kv_dtype=None):
         """Continue ``prompts`` [B, P] (right-padded; ``prompt_lens`` [B], default all P) by
         ``max_new_tokens`` tokens: LongTensor [B, max_new_tokens] (and the fp32 logits [B, T, V] each was
         chosen from, with ``return_logits``).  Greedy at temperature 0, else temperature / top-k sampling
         with ``torch.multinomial`` from ``generator``; a row that has emitted ``eos_id`` keeps emitting it.
-        Runs without gradients in eval mode with bf16 projections on a GPU (never FP8).  The token loop
+        Runs without gradients in eval mode with bf16 projections on a GPU (never FP8).  ``kv_dtype``: the
+        cache's dtype; ``torch.float8_e4m3fn`` halves its bytes and changes the numbers.  The token loop
         reads nothing back from the device; the one synchronisation is the caller's use of the result."""
         V = self.cfg.vocab_size
         if not isinstance(prompts, torch.Tensor) or prompts.dim() != 2 or prompts.dtype != torch.long or \
@@ -445,7 +465,7 @@ class Llama(nn.Module):
             TNLinear.impl = "tn"
         try:
             with torch.no_grad(), torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=amp_on):
-                cache = self.new_cache(B, max_len, torch.bfloat16 if amp_on else None)
+                cache = self.new_cache(B, max_len, kv_dtype or (torch.bfloat16 if amp_on else None))
                 self._rope(cache, max(max_len, self._prefill_len(P, dev)))  # the tables, once: the padded prompt's too
                 logits = self.prefill(prompts, lens, cache).float()
                 out, kept = [], []

@@ -201,6 +201,10 @@ _SIGNATURES = {
     # decode_attention.hip
     "pto_rope_append": [_VP] * 7 + [_L, _I, _I, _I, _I, _I, _I, _VP],
     "pto_decode_attn": [_VP] * 8 + [_I] * 7 + [_VP],
+    # decode_attention_fp8.hip
+    "pto_rope_append_fp8": [_VP] * 6 + [_I] + [_VP] * 3 + [_L, _I, _I, _I, _I, _I, _I, _VP],
+    "pto_kv_quantize": [_VP] * 6 + [_I, _L, _I, _I, _I, _I, _VP],
+    "pto_decode_attn_fp8": [_VP] * 5 + [_I] + [_VP] * 5 + [_I] * 7 + [_VP],
     # skinny_gemm.hip
     "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     # skinny_gemm_fp8.hip

@@ -15,6 +15,14 @@ past n never reach the result, whatever they hold.  ``impl``: "auto" = the HIP k
 unsupported shape is an error, never a silent fallback) and the PyTorch math on CPU; "sdpa" = the
 library path (``scaled_dot_product_attention`` over the cache with a length mask): the A/B baseline,
 and the path for shapes the kernel does not cover (fp32 caches, other head dims).
+
+An FP8 cache (``KVCache(..., dtype=torch.float8_e4m3fn)``, ``csrc/kernels/decode_attention_fp8.hip``):
+``k`` / ``v`` hold e4m3 codes in the same layout and ``k_scale`` / ``v_scale`` [L, B, Hkv, max_len_pad]
+one fp32 power-of-two scale per (token, kv head), by the rule of ``ops.skinny.quantize_rows`` applied to
+the bf16 row the bf16 cache would hold.  ``rope_append`` and ``decode_attention`` take the layer's scales as
+``k_scale`` / ``v_scale``; ``quantize_kv(k, v, ...)`` is the prefill's copy.  Dequantisation is exact in
+bf16: the attention is the bf16 attention on the dequantised cache.  q stays bf16; ``impl="sdpa"`` does not
+serve an FP8 cache.
 """
 from __future__ import annotations
 
@@ -27,20 +35,27 @@ import torch.nn.functional as F
 
 from . import _native
 from .llm import _DT, _aligned, _stream, rope_reference
+from .skinny import dequantize_rows, quantize_rows
 
 HEAD_DIMS = (64, 128)
 GROUPS = (1, 2, 4, 8)
+FP8 = torch.float8_e4m3fn
 
 
 class KVCache:
     """Keys and values of ``n_layers`` layers, ``k`` / ``v`` [L, B, max_len, Hkv, D], and ``lens``
-    int32 [B] (valid rows per batch row) on the same device."""
+    int32 [B] (valid rows per batch row) on the same device.  With ``dtype=torch.float8_e4m3fn`` also
+    ``k_scale`` / ``v_scale`` fp32 [L, B, Hkv, max_len rounded up to a multiple of 4] (else None)."""
 
     def __init__(self, n_layers: int, B: int, max_len: int, Hkv: int, D: int, dtype=torch.bfloat16, device=None):
         if min(n_layers, B, max_len, Hkv, D) <= 0:
             raise ValueError(f"KVCache: sizes must be positive, got {(n_layers, B, max_len, Hkv, D)}")
         self.k = torch.zeros(n_layers, B, max_len, Hkv, D, dtype=dtype, device=device)
         self.v = torch.zeros_like(self.k)
+        self.k_scale = self.v_scale = None
+        if dtype == FP8:
+            self.k_scale = torch.ones(n_layers, B, Hkv, -(-max_len // 4) * 4, dtype=torch.float32, device=device)
+            self.v_scale = torch.ones_like(self.k_scale)
         self.lens = torch.zeros(B, dtype=torch.int32, device=device)
         self.max_len = max_len
         self.rope = None  # (cos, sin) tables of the model that fills the cache, built on first use
@@ -58,13 +73,52 @@ def _check_cache(name, k_layer, v_layer, B, hkv, D):
         raise ValueError(f"{name}: the cache layers must be contiguous (they are written in place)")
 
 
+def _check_scales(name, k_layer, k_scale, v_scale) -> bool:
+    """True for an FP8 cache with its scales; a ``ValueError`` where cache and scales do not go together."""
+    if k_layer.dtype != FP8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError(f"{name}: k_scale / v_scale go with an e4m3 cache; the caches are {k_layer.dtype}")
+        return False
+    B, max_len, hkv, _ = k_layer.shape
+    for what, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is None:
+            raise ValueError(f"{name}: an e4m3 cache needs k_scale and v_scale (KVCache allocates them)")
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[:2] != (B, hkv) or t.shape[2] < max_len or \
+                t.shape[2] % 4 or t.device != k_layer.device or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous fp32 [B={B}, Hkv={hkv}, >= {max_len} and a multiple "
+                             f"of 4] on {k_layer.device}; got {t.dtype} {tuple(t.shape)} {t.device}")
+    if k_scale.shape != v_scale.shape:
+        raise ValueError(f"{name}: k_scale and v_scale differ in shape: {tuple(k_scale.shape)}, {tuple(v_scale.shape)}")
+    return True
+
+
+def _fp8_hip_ok(name, x, k_layer, v_layer, k_scale, v_scale, D):
+    if x.dtype != torch.bfloat16 or D not in HEAD_DIMS or any(
+            t.data_ptr() % 16 for t in (k_layer, v_layer, k_scale, v_scale)):
+        raise ValueError(f"{name}: the HIP path on an e4m3 cache needs bf16 input, D in {HEAD_DIMS} and 16-byte "
+                         f"aligned caches and scales; got {x.dtype}, D {D}")
+
+
+def _quantize_heads(x: torch.Tensor):
+    """[..., D] -> e4m3 codes of the bf16-rounded rows and their scales [...] (the PyTorch path)."""
+    q, s = quantize_rows(x.to(torch.bfloat16).reshape(-1, x.shape[-1]))
+    return q.view(x.shape), s.view(x.shape[:-1])
+
+
+def dequantize_cache(layer: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """An e4m3 cache layer [B, max_len, Hkv, D] and its scales [B, Hkv, >= max_len] -> the cache in ``dtype``
+    (exact in bf16 and wider)."""
+    s = scale[:, :, :layer.shape[1]].transpose(1, 2)
+    return dequantize_rows(layer.reshape(-1, layer.shape[-1]), s.reshape(-1), dtype).view(layer.shape)
+
+
 def _check_index(name, what, t, B, device):
     if t.dtype != torch.int32 or t.shape != (B,) or t.device != device:
         raise ValueError(f"{name}: {what} must be int32 [{B}] on {device}; got {t.dtype} {tuple(t.shape)} {t.device}")
 
 
 # ------------------------------------------------------------------------------ rope_append
-def rope_append_reference(qkv, cos, sin, k_layer, v_layer, pos, hq: int, hkv: int):
+def rope_append_reference(qkv, cos, sin, k_layer, v_layer, pos, hq: int, hkv: int, k_scale=None, v_scale=None):
     B, W = qkv.shape
     D = W // (hq + 2 * hkv)
     max_len = k_layer.shape[1]
@@ -78,14 +132,24 @@ def rope_append_reference(qkv, cos, sin, k_layer, v_layer, pos, hq: int, hkv: in
     ok = ((p >= 0) & (p < max_len)).view(B, 1, 1)
     bi, row = torch.arange(B, device=qkv.device), p.clamp(0, max_len - 1)
     # a position outside the cache rewrites row 0 / max_len - 1 with what it already holds
+    if k_layer.dtype == FP8:
+        hi = torch.arange(hkv, device=qkv.device)
+        for layer, scale, new in ((k_layer, k_scale, kr), (v_layer, v_scale, v.reshape(B, hkv, D))):
+            code, sc = _quantize_heads(new)
+            bytes_, at = layer.view(torch.uint8), (bi[:, None], hi[None, :], row[:, None])
+            bytes_[bi, row] = torch.where(ok, code.view(torch.uint8), bytes_[bi, row])
+            scale[at] = torch.where(ok.view(B, 1), sc, scale[at])
+        return qr
     k_layer[bi, row] = torch.where(ok, kr.to(k_layer.dtype), k_layer[bi, row])
     v_layer[bi, row] = torch.where(ok, v.reshape(B, hkv, D).to(v_layer.dtype), v_layer[bi, row])
     return qr
 
 
 def rope_append(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_layer: torch.Tensor,
-                v_layer: torch.Tensor, pos: torch.Tensor, hq: int, hkv: int) -> torch.Tensor:
-    """q [B, hq, D] rotated at ``pos``; k (rotated) and v go to cache row ``pos[b]`` in place."""
+                v_layer: torch.Tensor, pos: torch.Tensor, hq: int, hkv: int,
+                k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q [B, hq, D] rotated at ``pos``; k (rotated) and v go to cache row ``pos[b]`` in place -- quantised,
+    with their scales to ``k_scale`` / ``v_scale`` [B, hkv, max_len_pad], when the cache is e4m3."""
     if qkv.dim() != 2 or hq <= 0 or hkv <= 0 or qkv.shape[1] % (hq + 2 * hkv):
         raise ValueError(f"rope_append: qkv must be [B, (hq + 2 hkv) * D]; got {tuple(qkv.shape)} hq {hq} hkv {hkv}")
     B, W = qkv.shape
@@ -94,8 +158,18 @@ def rope_append(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_layer
     _check_index("rope_append", "pos", pos, B, qkv.device)
     if D % 8 or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.shape != sin.shape or cos.shape[0] < 1:
         raise ValueError(f"rope_append: D % 8 == 0 and tables [rows, D/2]; got D {D}, cos {tuple(cos.shape)}")
+    fp8 = _check_scales("rope_append", k_layer, k_scale, v_scale)
     if not qkv.is_cuda:
-        return rope_append_reference(qkv, cos, sin, k_layer, v_layer, pos, hq, hkv)
+        return rope_append_reference(qkv, cos, sin, k_layer, v_layer, pos, hq, hkv, k_scale, v_scale)
+    if fp8:
+        _fp8_hip_ok("rope_append", qkv, k_layer, v_layer, k_scale, v_scale, D)
+        qkv, cos, sin = _aligned(qkv), _aligned(cos.float()), _aligned(sin.float())
+        q = qkv.new_empty(B, hq, D)
+        _native.check(_native.load().pto_rope_append_fp8(
+            qkv.data_ptr(), q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), k_scale.data_ptr(),
+            v_scale.data_ptr(), k_scale.shape[2], cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), B, k_layer.shape[1],
+            cos.shape[0], hq, hkv, D, _DT[qkv.dtype], _stream(qkv)), "rope_append_fp8")
+        return q
     if qkv.dtype not in _DT or k_layer.dtype != qkv.dtype or k_layer.data_ptr() % 16 or v_layer.data_ptr() % 16:
         raise ValueError(f"rope_append: qkv and the caches must share fp32 or bf16 and be 16-byte aligned; got "
                          f"{qkv.dtype}, {k_layer.dtype}")
@@ -105,6 +179,34 @@ def rope_append(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_layer
         qkv.data_ptr(), q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), cos.data_ptr(), sin.data_ptr(),
         pos.data_ptr(), B, k_layer.shape[1], cos.shape[0], hq, hkv, D, _DT[qkv.dtype], _stream(qkv)), "rope_append")
     return q
+
+
+# ------------------------------------------------------------------------------ quantize_kv
+def quantize_kv(k: torch.Tensor, v: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor,
+                k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+    """The prefill's copy into an e4m3 cache: rows [0, n), n = min(S, max_len), of ``k`` / ``v`` [B, S, Hkv, D]
+    (as ``rope_qkv`` returns them) are rounded to bf16, quantised per (token, head) and stored with their
+    scales: byte for byte what ``rope_append`` stores for the same token at the same position."""
+    if k.dim() != 4 or k.shape != v.shape or k.dtype != v.dtype or k.device != k_layer.device:
+        raise ValueError(f"quantize_kv: k and v must be [B, S, Hkv, D] of one dtype on the cache's device; got "
+                         f"{tuple(k.shape)} {k.dtype}, {tuple(v.shape)} {v.dtype}")
+    B, S, hkv, D = k.shape
+    _check_cache("quantize_kv", k_layer, v_layer, B, hkv, D)
+    if not _check_scales("quantize_kv", k_layer, k_scale, v_scale):
+        raise ValueError(f"quantize_kv: the caches must be e4m3; got {k_layer.dtype}")
+    max_len = k_layer.shape[1]
+    n = min(S, max_len)
+    if not k.is_cuda:
+        for src, layer, scale in ((k, k_layer, k_scale), (v, v_layer, v_scale)):
+            code, sc = _quantize_heads(src[:, :n])
+            layer.view(torch.uint8)[:, :n] = code.view(torch.uint8)
+            scale[:, :, :n] = sc.transpose(1, 2)
+        return
+    _fp8_hip_ok("quantize_kv", k, k_layer, v_layer, k_scale, v_scale, D)
+    k, v = _aligned(k), _aligned(v)
+    _native.check(_native.load().pto_kv_quantize(
+        k.data_ptr(), v.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+        k_scale.shape[2], B, S, max_len, hkv, D, _stream(k)), "kv_quantize")
 
 
 # -------------------------------------------------------------------------- decode_attention
@@ -151,7 +253,8 @@ def hip_supported(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor)
         return False
     B, hq, D = q.shape
     hkv = k_layer.shape[2]
-    return (q.dtype == k_layer.dtype == v_layer.dtype == torch.bfloat16 and D in HEAD_DIMS and hkv > 0
+    return (q.dtype == torch.bfloat16 and k_layer.dtype == v_layer.dtype and k_layer.dtype in (torch.bfloat16, FP8)
+            and D in HEAD_DIMS and hkv > 0
             and hq % hkv == 0 and hq // hkv in GROUPS and B <= 65535 and hkv <= 65535)
 
 
@@ -170,7 +273,8 @@ def _partials(device, floats: int) -> torch.Tensor:
 
 
 def decode_attention(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor, lens: torch.Tensor,
-                     max_keys: Optional[int] = None, impl: str = "auto") -> torch.Tensor:
+                     max_keys: Optional[int] = None, impl: str = "auto",
+                     k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     if impl not in ("auto", "sdpa"):
         raise ValueError(f"decode_attention: impl must be 'auto' or 'sdpa', got {impl!r}")
     if q.dim() != 3 or k_layer.dim() != 4 or k_layer.shape[2] <= 0 or q.shape[1] % max(k_layer.shape[2], 1):
@@ -184,16 +288,24 @@ def decode_attention(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tens
         max_keys = max_len
     if not isinstance(max_keys, int) or not 1 <= max_keys <= max_len:
         raise ValueError(f"decode_attention: max_keys must be an int in [1, max_len = {max_len}], got {max_keys!r}")
-    if q.dtype != k_layer.dtype:
+    fp8 = _check_scales("decode_attention", k_layer, k_scale, v_scale)
+    if fp8 and impl == "sdpa":
+        raise ValueError("decode_attention: impl='sdpa' does not serve an e4m3 cache (the library path needs q and "
+                         "the cache in one dtype)")
+    if not fp8 and q.dtype != k_layer.dtype:
         raise ValueError(f"decode_attention: q and the caches must share a dtype; got {q.dtype}, {k_layer.dtype}")
     if not q.is_cuda:
+        if fp8:  # rows past the lengths may hold anything, NaN codes and scales included: selection hides them
+            k_layer, v_layer = dequantize_cache(k_layer, k_scale, q.dtype), dequantize_cache(v_layer, v_scale, q.dtype)
         return decode_attention_reference(q, k_layer, v_layer, lens, max_keys)
     if impl == "sdpa":
         return decode_attention_sdpa(q, k_layer, v_layer, lens, max_keys)
     if not hip_supported(q, k_layer, v_layer) or k_layer.data_ptr() % 16 or v_layer.data_ptr() % 16:
-        raise ValueError(f"decode_attention: the HIP path needs bf16, D in {HEAD_DIMS}, Hq / Hkv in {GROUPS} and "
-                         f"16-byte aligned caches (impl='sdpa' serves other shapes); got q {tuple(q.shape)} "
-                         f"{q.dtype}, caches {tuple(k_layer.shape)}")
+        raise ValueError(f"decode_attention: the HIP path needs bf16 (or a bf16 q with e4m3 caches), D in {HEAD_DIMS}, "
+                         f"Hq / Hkv in {GROUPS} and 16-byte aligned caches (impl='sdpa' serves other shapes); got q "
+                         f"{tuple(q.shape)} {q.dtype}, caches {tuple(k_layer.shape)} {k_layer.dtype}")
+    if fp8:
+        _fp8_hip_ok("decode_attention", q, k_layer, v_layer, k_scale, v_scale, D)
     lib = _native.load()
     q = _aligned(q)
     nchunks = -(-max_keys // int(lib.pto_decode_chunk()))
@@ -201,6 +313,12 @@ def decode_attention(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tens
     ws = _partials(q.device, rows * (D + 2))
     po, pm, pl = ws[:rows * D], ws[rows * D:rows * (D + 1)], ws[rows * (D + 1):rows * (D + 2)]
     o = torch.empty_like(q)
+    if fp8:
+        _native.check(lib.pto_decode_attn_fp8(q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), k_scale.data_ptr(),
+                                              v_scale.data_ptr(), k_scale.shape[2], lens.data_ptr(), o.data_ptr(),
+                                              po.data_ptr(), pm.data_ptr(), pl.data_ptr(), B, max_len, max_keys, hq,
+                                              k_layer.shape[2], D, nchunks, _stream(q)), "decode_attn_fp8")
+        return o
     _native.check(lib.pto_decode_attn(q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), lens.data_ptr(),
                                       o.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), B, max_len,
                                       max_keys, hq, k_layer.shape[2], D, nchunks, _stream(q)), "decode_attn")

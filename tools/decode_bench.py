@@ -23,6 +23,12 @@ alternating, two runs each; the prefill runs the HIP flash attention both times.
 the attention stays on the HIP kernels and the decode step's projections change sides instead (the library
 GEMMs + a SwiGLU launch against ``ops.skinny.linear_rows``), each run checked by ``TNLinear.rows_calls``.
 
+--kv fp8: the e4m3 cache of ``csrc/kernels/decode_attention_fp8.hip`` against the bf16 cache.  Kernel mode: "fp8"
+and "hip" (the bf16 kernel) alternate, two runs each, over caches of equal shape; each side's "gbps" counts its own
+bytes, the fp8 side's scales included, and the layers are sized so that the e4m3 caches alone exceed 512 MiB.
+--e2e --kv fp8: ``Llama.generate`` with ``kv_dtype=torch.float8_e4m3fn`` against the bf16 cache, with the peak of
+``torch.cuda.max_memory_allocated`` per side ("*_peak_mb").
+
 --linear: ``ops.skinny.linear_rows`` against ``F.linear`` (+ ``swiglu_packed`` for w13) on the same tensors, at
 the five projection shapes of llama3-8b and llama3-1b and M = --rows.  The calls cycle through enough copies
 of the weight to exceed 512 MiB, so every call streams its weight from HBM ("gbps" = bytes of W / time, "peak"
@@ -59,6 +65,38 @@ def timed(fn, layers, reps):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1e3 / reps, host * 1e6 / reps
+
+
+def kernel_fp8_bench(a):
+    from pytorch_operator_amd.ops.decode import FP8, KVCache, decode_attention, quantize_kv
+    out = []
+    for D in a.head_dim:
+        for B in a.batch:
+            for n in a.keys:
+                own = {"hip": 2 * B * n * a.hkv * D * 2, "fp8": 2 * B * n * a.hkv * (D + 4)}
+                L = max(1, min(64, -(-(512 << 20) // own["fp8"])))
+                cache, cache8 = KVCache(L, B, n, a.hkv, D, torch.bfloat16, "cuda"), KVCache(L, B, n, a.hkv, D, FP8, "cuda")
+                for i in range(L):
+                    cache.k[i].normal_()
+                    cache.v[i].normal_()
+                    quantize_kv(cache.k[i], cache.v[i], cache8.k[i], cache8.v[i], cache8.k_scale[i], cache8.v_scale[i])
+                lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+                q = torch.randn(B, a.hq, D, device="cuda").to(torch.bfloat16)
+                fns = {"hip": lambda i: decode_attention(q, cache.k[i], cache.v[i], lens),
+                       "fp8": lambda i: decode_attention(q, cache8.k[i], cache8.v[i], lens, k_scale=cache8.k_scale[i],
+                                                         v_scale=cache8.v_scale[i])}
+                row = {"B": B, "n": n, "Hq": a.hq, "Hkv": a.hkv, "D": D, "layers": L,
+                       "footprint_mb": round(L * own["hip"] / 1e6, 1), "fp8_footprint_mb": round(L * own["fp8"] / 1e6, 1)}
+                for name in ("fp8", "hip", "fp8", "hip"):
+                    dev_us, host_us = timed(fns[name], L, a.reps)
+                    row.setdefault(name + "_us", []).append(round(dev_us, 2))
+                    row.setdefault(name + "_host_us", []).append(round(host_us, 2))
+                for name in ("fp8", "hip"):
+                    row[name + "_gbps"] = round(own[name] / min(row[name + "_us"]) / 1e3, 1)
+                print(json.dumps(row), flush=True)
+                out.append(row)
+                del cache, cache8
+    return out
 
 
 def kernel_bench(a):
@@ -210,24 +248,29 @@ def e2e_bench(a):
         for B in a.batch:
             prompts = torch.randint(0, model.cfg.vocab_size, (B, a.prompt), device="cuda")
             row = {"model": name, "B": B, "prompt": a.prompt, "new_tokens": a.tokens}
-            for impl in ("warm", "hip", "sdpa", "hip", "sdpa"):
+            other = "hip-fp8" if a.kv == "fp8" else "sdpa"
+            for impl in ("warm", "hip", other, "hip", other):
                 # the decode step alone changes sides: Attention.impl would move the prefill as well
                 Attention.decode_impl = "sdpa" if impl == "sdpa" else None
                 Attention.decode_calls.clear()
+                torch.cuda.reset_peak_memory_stats()
                 try:
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    toks = model.generate(prompts, max_new_tokens=a.tokens)
+                    toks = model.generate(prompts, max_new_tokens=a.tokens,
+                                          kv_dtype=torch.float8_e4m3fn if impl == "hip-fp8" else None)
                     torch.cuda.synchronize()
                     dt = time.perf_counter() - t0
                 finally:
                     Attention.decode_impl = None
                 # every decode step of the run took the side it is reported under
-                want = "sdpa" if impl == "sdpa" else "hip"
+                want = "hip" if impl == "warm" else impl
                 assert dict(Attention.decode_calls) == {want: (a.tokens - 1) * model.cfg.n_layers}, Attention.decode_calls
                 if impl != "warm":
                     row.setdefault(impl + "_tokens_per_s", []).append(round(B * a.tokens / dt, 1))
                     row.setdefault(impl + "_ms_per_token", []).append(round(dt / a.tokens * 1e3, 3))
+                    if a.kv == "fp8":
+                        row.setdefault(impl + "_peak_mb", []).append(round(torch.cuda.max_memory_allocated() / 1e6, 1))
             assert toks.shape == (B, a.tokens) and Attention.impl == "auto"
             print(json.dumps(row), flush=True)
             out.append(row)
@@ -255,12 +298,16 @@ def main():
                    help="--e2e: the sides of the projection A/B, e.g. lib,hip or lib,hip,hip-fp8 (default: the "
                         "attention A/B); --linear: the sides in their order (default hip,lib)")
     p.add_argument("--fp8-tiles", type=ints, default=[], help="--linear with hip-fp8: also each forced tile count")
+    p.add_argument("--kv", choices=["bf16", "fp8"], default="bf16",
+                   help="fp8: the e4m3 KV cache against the bf16 one (kernel mode and --e2e without --decode-linear)")
     p.add_argument("--json-out", default=None)
     a = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: needs a GPU (a CPU timing says nothing about these kernels)")
     if a.decode_linear and (not (a.e2e or a.linear) or set(a.decode_linear) - {"lib", "hip", "hip-fp8"}):
         p.error("--decode-linear takes lib, hip and / or hip-fp8, with --e2e or --linear")
+    if a.kv == "fp8" and (a.linear or a.decode_linear):
+        p.error("--kv fp8 goes with the kernel mode or the attention --e2e")
     if set(a.fp8_tiles) - {1, 2, 4}:
         p.error("--fp8-tiles takes 1, 2 and / or 4")
     if a.linear:
@@ -268,7 +315,7 @@ def main():
     elif a.e2e:
         res = {"e2e_linear": e2e_linear_bench(a)} if a.decode_linear else {"e2e": e2e_bench(a)}
     else:
-        res = {"kernel": kernel_bench(a)}
+        res = {"kernel_fp8": kernel_fp8_bench(a)} if a.kv == "fp8" else {"kernel": kernel_bench(a)}
     if a.json_out:
         Path(a.json_out).write_text(json.dumps(res, indent=1) + "\n")
 
