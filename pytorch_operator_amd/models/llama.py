@@ -20,6 +20,8 @@ each, fwd and bwd).  On CPU the same math runs in PyTorch.
 
 ``Llama.generate`` writes text: ``prefill`` fills a KV cache from the prompts, ``decode_step`` appends
 one token per sequence and attends over the cache with the single-query HIP kernels of ``ops.decode``.
+``decode_steps`` appends several tokens per sequence in one step (the multi-query MFMA kernel); with a
+``draft`` model ``generate`` uses it to verify the draft's tokens (greedy speculative decoding).
 """
 from __future__ import annotations
 
@@ -199,8 +201,8 @@ class Attention(nn.Module):
     head dim 64 or 128, ...), the library's ``scaled_dot_product_attention`` otherwise -- an fp32 model
     called without autocast, for instance, runs the library path on a GPU without an error (the
     ``ops`` wrappers themselves never fall back).  ``decode_calls`` counts the decode steps per path
-    ("hip", "hip-fp8" on an e4m3 cache, "sdpa", "cpu"), so that a benchmark or a test can assert which one
-    it ran."""
+    ("hip", "hip-fp8" on an e4m3 cache, "hip-rows" for a multi-token step, "sdpa", "cpu"), so that a benchmark
+    or a test can assert which one it ran."""
 
     impl = "auto"  # "auto": HIP flash attention where it applies; "sdpa": library kernels
     decode_impl = None  # the decode step alone: None follows impl; "sdpa" / "auto" for A/B runs (tools/decode_bench.py)
@@ -217,7 +219,9 @@ class Attention(nn.Module):
     def forward(self, x, cos, sin, doc_start=None, cache=None):
         """``cache`` (a ``LayerCache``): S > 1 is a prefill -- the rotated k and v also go to the layer's
         cache rows [0, S); S == 1 is a decode step -- k and v are appended at row ``cache.pos[b]`` and
-        the one query attends to the ``cache.lens[b]`` rows of the cache (``ops.decode``)."""
+        the one query attends to the ``cache.lens[b]`` rows of the cache (``ops.decode``); S > 1 with
+        ``cache.pos`` set is a multi-token step -- rows ``pos[b]`` .. ``pos[b] + S - 1`` are appended and query s
+        attends to ``cache.lens[b] - (S - 1 - s)`` rows (``ops.decode.append_rows`` / ``attend_rows``)."""
         B, S, _ = x.shape
         from ..ops import attention as A
         from ..ops.llm import rope_qkv
@@ -232,6 +236,14 @@ class Attention(nn.Module):
             o = Dc.decode_attention(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
                                     cache.k_scale, cache.v_scale)
             return self.wo(o.reshape(B, 1, self.nh * self.hd))
+        if cache is not None and cache.pos is not None:
+            # S tokens per sequence appended at pos .. pos + S - 1, each attending to the rows up to its own
+            from ..ops import decode as Dc
+            q = Dc.append_rows(self.wqkv(x), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv)
+            hip = (self.decode_impl or self.impl) != "sdpa" and (not q.is_cuda or Dc.rows_supported(q, cache.k, cache.v))
+            Attention.decode_calls["cpu" if not q.is_cuda else ("hip-rows" if hip else "sdpa")] += 1
+            o = Dc.attend_rows(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa")
+            return self.wo(o.reshape(B, S, self.nh * self.hd))
         q, k, v = rope_qkv(self.wqkv(x), cos, sin, self.nh, self.nkv)
         if cache is not None:
             n = min(S, cache.k.shape[1])  # a prompt padded to the attention kernels' multiple may end past the cache
@@ -420,16 +432,95 @@ class Llama(nn.Module):
         cache.lens = lens
         return logits[:, 0]
 
+    def decode_steps(self, tokens: torch.Tensor, cache, max_keys: Optional[int] = None) -> torch.Tensor:
+        """Append S tokens per row (``tokens`` [B, S]) at positions ``cache.lens`` .. ``+ S - 1`` in one step
+        and return the logits [B, S, V] after each of them: token s attends to the cache rows up to its own.
+        ``cache.lens`` grows by S; ``max_keys`` bounds the lengths after the append, as in ``decode_step``.
+        The multi-query kernels of ``ops.decode`` take S * n_heads / n_kv_heads <= 16 on a bf16 cache (the
+        library path serves the rest); the projections take ``rows_linear``'s choice for B * S rows."""
+        if tokens.dim() != 2 or tokens.shape[1] < 1:
+            raise ValueError(f"decode_steps: tokens must be [B, S] with S >= 1, got {tuple(tokens.shape)}")
+        pos = cache.lens
+        lens = pos + tokens.shape[1]
+        mk = cache.max_len if max_keys is None else max_keys
+        cos, sin = self._rope(cache, cache.max_len)
+        h, d = self.tok_embeddings(tokens), None
+        for i, blk in enumerate(self.layers):
+            h, d = blk(h, d, cos, sin, None, self._layer_cache(cache, i, pos, lens, mk))
+        logits = self._lm_head(self.norm.add_forward(h, d)[1])
+        cache.lens = lens
+        return logits
+
+    def _speculate(self, draft, k: int, prompts, lens, cache, T: int, eos_id, return_logits: bool):
+        """The token loop of ``generate`` with a draft model (greedy).  A round: the draft takes k + 1 single
+        steps from the last emitted token (its cache then holds all k drafts), the target verifies
+        [last, d_1 .. d_k] in one ``decode_steps``, and a sequence emits the target's tokens t_1 .. t_(a+1),
+        a = the length of the prefix on which drafts and target agree.  Both caches' ``lens`` go back to
+        base + a + 1 on the device: the rows past that are dead and the next round overwrites them.  The
+        sequences advance raggedly; the one host read per round is the smallest emitted count."""
+        B, P = prompts.shape
+        dev, V = prompts.device, self.cfg.vocab_size
+        dcache = draft.new_cache(B, cache.max_len, cache.k.dtype)
+        draft._rope(dcache, max(cache.max_len, draft._prefill_len(P, dev)))
+        draft.prefill(prompts, lens, dcache)
+        logits = self.prefill(prompts, lens, cache).float()
+        width = T + k + 1                                    # a round may run k tokens past T; the last column is a dump
+        out = torch.zeros(B, width, dtype=torch.long, device=dev)
+        kept = torch.zeros(B * width, V, dtype=torch.float32, device=dev) if return_logits else None
+        ar = torch.arange(k + 1, device=dev).view(1, -1)
+        rows = torch.arange(B, device=dev).view(-1, 1) * width
+        last = logits.argmax(-1)                             # emitted, not yet in either cache
+        done = last == eos_id if eos_id is not None else None
+        out[:, 0] = last
+        if return_logits:
+            kept.index_copy_(0, rows[:, 0], logits)
+        cnt = torch.ones(B, dtype=torch.long, device=dev)   # tokens emitted per sequence
+        r = 0
+        while int(cnt.min()) < T:
+            base, seen = cache.lens, P + r * (k + 1)         # every length is at most `seen` before this round
+            toks, cur = [last], last
+            for j in range(k + 1):
+                dl = draft.decode_step(cur, dcache, max_keys=min(seen + j + 1, cache.max_len))
+                if j < k:
+                    cur = dl.argmax(-1)
+                    toks.append(cur)
+            toks = torch.stack(toks, dim=1)                  # [B, k + 1]: last, d_1 .. d_k
+            logits = self.decode_steps(toks, cache, max_keys=min(seen + k + 1, cache.max_len)).float()
+            t = logits.argmax(-1)                            # t_1 .. t_(k+1)
+            if eos_id is not None:                           # after an eos, emitted now or earlier, only eos
+                hit = (t == eos_id).long().cumsum(1)
+                t = torch.where(done.view(-1, 1) | (hit - (t == eos_id).long() > 0), eos_id, t)
+            a = (toks[:, 1:] == t[:, :k]).long().cumprod(1).sum(1)
+            a = torch.where(cnt < T, a, -1)                  # a sequence that has its tokens stands still
+            keep = ar <= a.view(-1, 1)
+            idx = torch.where(keep, cnt.view(-1, 1) + ar, width - 1)
+            out.scatter_(1, idx, t)
+            if return_logits:
+                kept.index_copy_(0, (rows + idx).view(-1), logits.reshape(-1, V))
+            if eos_id is not None:
+                done = done | ((t == eos_id) & keep).any(1)
+            last = torch.where(a >= 0, t.gather(1, a.clamp(min=0).view(-1, 1))[:, 0], last)
+            cnt = cnt + a + 1
+            cache.lens = dcache.lens = base + (a + 1).to(torch.int32)
+            r += 1
+        return out[:, :T], (kept.view(B, width, V)[:, :T] if return_logits else None)
+
     def generate(self, prompts: torch.Tensor, prompt_lens=None, max_new_tokens: int = 32, temperature: float = 0.0,
                  top_k: int = 0, eos_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 return_logits: bool = False, max_len: Optional[int] = None, kv_dtype=None):
+                 return_logits: bool = False, max_len: Optional[int] = None, kv_dtype=None,
+                 draft: Optional["Llama"] = None, draft_tokens: int = 0):
         """Continue ``prompts`` [B, P] (right-padded; ``prompt_lens`` [B], default all P) by
         ``max_new_tokens`` tokens: LongTensor [B, max_new_tokens] (and the fp32 logits [B, T, V] each was
         chosen from, with ``return_logits``).  Greedy at temperature 0, else temperature / top-k sampling
         with ``torch.multinomial`` from ``generator``; a row that has emitted ``eos_id`` keeps emitting it.
         Runs without gradients in eval mode with bf16 projections on a GPU (never FP8).  ``kv_dtype``: the
         cache's dtype; ``torch.float8_e4m3fn`` halves its bytes and changes the numbers.  The token loop
-        reads nothing back from the device; the one synchronisation is the caller's use of the result."""
+        reads nothing back from the device; the one synchronisation is the caller's use of the result.
+
+        ``draft`` (another ``Llama`` with the same vocabulary, on the same device) and ``draft_tokens`` = k >= 1:
+        greedy speculative decoding, see ``_speculate``.  The tokens are the target's own greedy choices, each
+        the argmax of the logits returned for it; a round costs one multi-token target step and k + 1 draft
+        steps, and one host read.  The caches hold up to P + max_new_tokens + k rows."""
         V = self.cfg.vocab_size
         if not isinstance(prompts, torch.Tensor) or prompts.dim() != 2 or prompts.dtype != torch.long or \
                 prompts.shape[1] < 1:
@@ -444,10 +535,24 @@ class Llama(nn.Module):
             raise ValueError(f"generate: top_k must be in [0, {V}] (0 = off), got {top_k!r}")
         if eos_id is not None and not 0 <= eos_id < V:
             raise ValueError(f"generate: eos_id {eos_id} is not an id of the {V}-token vocabulary")
-        max_len = P + T if max_len is None else max_len
-        if not P + T <= max_len <= self.cfg.max_seq_len:
-            raise ValueError(f"generate: need P + max_new_tokens = {P + T} <= max_len = {max_len} <= "
-                             f"max_seq_len = {self.cfg.max_seq_len}")
+        k = draft_tokens
+        if draft is None and k != 0:
+            raise ValueError(f"generate: draft_tokens = {k!r} needs a draft model")
+        if draft is not None:
+            if not isinstance(draft, Llama) or draft.cfg.vocab_size != V or not isinstance(k, int) or k < 1:
+                raise ValueError(f"generate: draft must be a Llama with the same {V}-token vocabulary and "
+                                 f"draft_tokens >= 1, got {type(draft).__name__} and {k!r}")
+            if temperature > 0.0:
+                raise ValueError("generate: a draft model goes with greedy decoding (temperature 0)")
+            if kv_dtype == torch.float8_e4m3fn:
+                raise ValueError("generate: the multi-token step of a draft round has no e4m3 cache path")
+            if draft.tok_embeddings.weight.device != self.tok_embeddings.weight.device:
+                raise ValueError("generate: draft and target must be on one device")
+        max_len = P + T + k if max_len is None else max_len  # a draft round may write k rows past the last token
+        if not P + T + k <= max_len <= min(self.cfg.max_seq_len, draft.cfg.max_seq_len if draft else max_len):
+            raise ValueError(f"generate: need P + max_new_tokens + draft_tokens = {P + T + k} <= max_len = {max_len} "
+                             f"<= max_seq_len = {self.cfg.max_seq_len}" +
+                             (f" and the draft's {draft.cfg.max_seq_len}" if draft else ""))
         # host-side checks of the prompt, before the loop
         host_lens = [P] * B if prompt_lens is None else [int(n) for n in torch.as_tensor(prompt_lens).cpu().tolist()]
         if len(host_lens) != B or min(host_lens) < 1 or max(host_lens) > P:
@@ -460,13 +565,19 @@ class Llama(nn.Module):
         lens = torch.tensor(host_lens, dtype=torch.int32, device=dev)
         amp_on = dev.type == "cuda" or self._low_precision(dev)
         was_training, linear_impl = self.training, TNLinear.impl
+        draft_training = draft.training if draft is not None else False
         self.eval()
+        if draft is not None:
+            draft.eval()
         if TNLinear.impl == "fp8":
             TNLinear.impl = "tn"
         try:
             with torch.no_grad(), torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=amp_on):
                 cache = self.new_cache(B, max_len, kv_dtype or (torch.bfloat16 if amp_on else None))
                 self._rope(cache, max(max_len, self._prefill_len(P, dev)))  # the tables, once: the padded prompt's too
+                if draft is not None:
+                    tokens, kept = self._speculate(draft, k, prompts, lens, cache, T, eos_id, return_logits)
+                    return (tokens, kept) if return_logits else tokens
                 logits = self.prefill(prompts, lens, cache).float()
                 out, kept = [], []
                 done = torch.zeros(B, dtype=torch.bool, device=dev)
@@ -489,5 +600,7 @@ class Llama(nn.Module):
         finally:
             TNLinear.impl = linear_impl
             self.train(was_training)
+            if draft is not None:
+                draft.train(draft_training)
         tokens = torch.stack(out, dim=1)
         return (tokens, torch.stack(kept, dim=1)) if return_logits else tokens

@@ -205,6 +205,9 @@ _SIGNATURES = {
     "pto_rope_append_fp8": [_VP] * 6 + [_I] + [_VP] * 3 + [_L, _I, _I, _I, _I, _I, _I, _VP],
     "pto_kv_quantize": [_VP] * 6 + [_I, _L, _I, _I, _I, _I, _VP],
     "pto_decode_attn_fp8": [_VP] * 5 + [_I] + [_VP] * 5 + [_I] * 7 + [_VP],
+    # decode_attention_multi.hip
+    "pto_rope_append_multi": [_VP] * 7 + [_L] + [_I] * 7 + [_VP],
+    "pto_decode_attn_multi": [_VP] * 8 + [_I] * 8 + [_VP],
     # skinny_gemm.hip
     "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     # skinny_gemm_fp8.hip
@@ -254,7 +257,7 @@ _SIGNATURES = {
 }
 _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_parts": [_L, _I],
              "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
-             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": [],
+             "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": [], "pto_decode_multi_rows": [],
              "pto_skinny_max_rows": [], "pto_skinny_waves": [_I],
              "pto_skinny_fp8_waves": [_I], "pto_skinny_fp8_tiles": [_I, _I, _I]}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}

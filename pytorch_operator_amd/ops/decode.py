@@ -23,6 +23,9 @@ the bf16 row the bf16 cache would hold.  ``rope_append`` and ``decode_attention`
 ``k_scale`` / ``v_scale``; ``quantize_kv(k, v, ...)`` is the prefill's copy.  Dequantisation is exact in
 bf16: the attention is the bf16 attention on the dequantised cache.  q stays bf16; ``impl="sdpa"`` does not
 serve an FP8 cache.
+
+``append_rows`` / ``attend_rows`` (``csrc/kernels/decode_attention_multi.hip``) are the same two steps for S tokens
+per sequence; see the end of this file.
 """
 from __future__ import annotations
 
@@ -322,4 +325,122 @@ def decode_attention(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tens
     _native.check(lib.pto_decode_attn(q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), lens.data_ptr(),
                                       o.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), B, max_len,
                                       max_keys, hq, k_layer.shape[2], D, nchunks, _stream(q)), "decode_attn")
+    return o
+
+
+# ------------------------------------------------------------- S tokens per sequence in one step
+# csrc/kernels/decode_attention_multi.hip: a step over S tokens per sequence (the verification step of
+# speculative decoding, or a few tokens appended to an existing cache).  ``append_rows`` is ``rope_append`` for
+# qkv [B, S, W]: token s of sequence b is rotated at ``pos[b] + s`` and stored at that cache row (a row outside
+# the cache stores nothing, token by token).  ``attend_rows`` is ``decode_attention`` for q [B, S, Hq, D]: query s
+# sees the keys j < n_s, n_s = min(lens[b], max_keys) - (S - 1 - s), ``lens`` counting the rows after the append;
+# n_s <= 0 gives a zero row.  The HIP kernel takes the S * Hq / Hkv query rows of a kv head as the 16 columns of
+# one MFMA tile: bf16, D in HEAD_DIMS, S * Hq / Hkv <= MAX_QUERY_ROWS; ``impl="sdpa"`` serves the rest.  The e4m3
+# cache has no multi-token path.
+MAX_QUERY_ROWS = 16
+
+
+def _row_lens(lens, max_keys: int, S: int, s: int) -> torch.Tensor:
+    return lens.clamp(max=max_keys) - (S - 1 - s)
+
+
+def append_rows(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_layer: torch.Tensor,
+                v_layer: torch.Tensor, pos: torch.Tensor, hq: int, hkv: int) -> torch.Tensor:
+    """q [B, S, hq, D], token s rotated at ``pos[b] + s``; its k (rotated) and v go to that cache row in place."""
+    if qkv.dim() != 3 or hq <= 0 or hkv <= 0 or qkv.shape[1] < 1 or qkv.shape[2] % (hq + 2 * hkv):
+        raise ValueError(f"append_rows: qkv must be [B, S, (hq + 2 hkv) * D]; got {tuple(qkv.shape)} hq {hq} hkv {hkv}")
+    B, S, W = qkv.shape
+    D = W // (hq + 2 * hkv)
+    _check_cache("append_rows", k_layer, v_layer, B, hkv, D)
+    _check_index("append_rows", "pos", pos, B, qkv.device)
+    if D % 8 or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.shape != sin.shape or cos.shape[0] < 1:
+        raise ValueError(f"append_rows: D % 8 == 0 and tables [rows, D/2]; got D {D}, cos {tuple(cos.shape)}")
+    if k_layer.dtype == FP8:
+        raise ValueError("append_rows: an e4m3 cache takes one token per step (rope_append); S tokens need a bf16 "
+                         "or fp32 cache")
+    if not qkv.is_cuda:
+        return torch.stack([rope_append_reference(qkv[:, s], cos, sin, k_layer, v_layer, pos + s, hq, hkv)
+                            for s in range(S)], dim=1)
+    if qkv.dtype not in _DT or k_layer.dtype != qkv.dtype or k_layer.data_ptr() % 16 or v_layer.data_ptr() % 16:
+        raise ValueError(f"append_rows: qkv and the caches must share fp32 or bf16 and be 16-byte aligned; got "
+                         f"{qkv.dtype}, {k_layer.dtype}")
+    qkv, cos, sin = _aligned(qkv), _aligned(cos.float()), _aligned(sin.float())
+    q = qkv.new_empty(B, S, hq, D)
+    _native.check(_native.load().pto_rope_append_multi(
+        qkv.data_ptr(), q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+        pos.data_ptr(), B, S, k_layer.shape[1], cos.shape[0], hq, hkv, D, _DT[qkv.dtype], _stream(qkv)),
+        "rope_append_multi")
+    return q
+
+
+def attend_rows_sdpa(q, k_layer, v_layer, lens, max_keys: int) -> torch.Tensor:
+    """The library path: the S * G query rows of a kv head are the "sequence" of one SDPA call with a mask per
+    row; rows past the lengths are replaced by zeros first and rows without a key give zeros."""
+    B, S, hq, D = q.shape
+    hkv = k_layer.shape[2]
+    G = hq // hkv
+    n = torch.stack([_row_lens(lens, max_keys, S, s) for s in range(S)], dim=1)            # [B, S]
+    keys = torch.arange(max_keys, device=q.device).view(1, 1, -1)
+    mask = (keys < n.view(B, S, 1)).view(B, 1, S, 1, max_keys).expand(B, 1, S, G, max_keys)
+    sel = _valid(lens, max_keys).view(B, max_keys, 1, 1)
+    k = torch.where(sel, k_layer[:, :max_keys], 0.0).transpose(1, 2)                       # [B, hkv, mk, D]
+    v = torch.where(sel, v_layer[:, :max_keys], 0.0).transpose(1, 2)
+    qs = q.view(B, S, hkv, G, D).permute(0, 2, 1, 3, 4).reshape(B, hkv, S * G, D)
+    o = F.scaled_dot_product_attention(qs, k, v, attn_mask=mask.reshape(B, 1, S * G, max_keys))
+    o = o.view(B, hkv, S, G, D).permute(0, 2, 1, 3, 4).reshape(B, S, hq, D)
+    return torch.where((n > 0).view(B, S, 1, 1), o, 0.0)
+
+
+def rows_supported(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor) -> bool:
+    """The HIP ``attend_rows`` serves q [B, S, Hq, D] over these caches."""
+    if not (q.is_cuda and k_layer.is_cuda and v_layer.is_cuda) or q.dim() != 4 or k_layer.dim() != 4:
+        return False
+    B, S, hq, D = q.shape
+    hkv = k_layer.shape[2]
+    return (q.dtype == torch.bfloat16 and k_layer.dtype == torch.bfloat16 and v_layer.dtype == torch.bfloat16
+            and D in HEAD_DIMS and hkv > 0 and S >= 1 and hq % hkv == 0 and S * (hq // hkv) <= MAX_QUERY_ROWS
+            and B <= 65535 and hkv <= 65535)
+
+
+def attend_rows(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor, lens: torch.Tensor,
+                max_keys: Optional[int] = None, impl: str = "auto") -> torch.Tensor:
+    """o [B, S, Hq, D]: query s of sequence b over the first n_s = min(lens[b], max_keys) - (S - 1 - s) cache rows."""
+    if impl not in ("auto", "sdpa"):
+        raise ValueError(f"attend_rows: impl must be 'auto' or 'sdpa', got {impl!r}")
+    if q.dim() != 4 or k_layer.dim() != 4 or k_layer.shape[2] <= 0 or q.shape[1] < 1 or \
+            q.shape[2] % max(k_layer.shape[2], 1):
+        raise ValueError(f"attend_rows: q [B, S, Hq, D] and caches [B, max_len, Hkv, D] with Hq % Hkv == 0; got "
+                         f"{tuple(q.shape)}, {tuple(k_layer.shape)}")
+    B, S, hq, D = q.shape
+    _check_cache("attend_rows", k_layer, v_layer, B, k_layer.shape[2], D)
+    _check_index("attend_rows", "lens", lens, B, q.device)
+    max_len = k_layer.shape[1]
+    if max_keys is None:
+        max_keys = max_len
+    if not isinstance(max_keys, int) or not 1 <= max_keys <= max_len:
+        raise ValueError(f"attend_rows: max_keys must be an int in [1, max_len = {max_len}], got {max_keys!r}")
+    if k_layer.dtype == FP8:
+        raise ValueError("attend_rows: an e4m3 cache takes one query per step (decode_attention)")
+    if q.dtype != k_layer.dtype:
+        raise ValueError(f"attend_rows: q and the caches must share a dtype; got {q.dtype}, {k_layer.dtype}")
+    if not q.is_cuda:
+        return torch.stack([decode_attention_reference(q[:, s], k_layer, v_layer, _row_lens(lens, max_keys, S, s),
+                                                       max_keys) for s in range(S)], dim=1)
+    if impl == "sdpa":
+        return attend_rows_sdpa(q, k_layer, v_layer, lens, max_keys)
+    if not rows_supported(q, k_layer, v_layer) or k_layer.data_ptr() % 16 or v_layer.data_ptr() % 16:
+        raise ValueError(f"attend_rows: the HIP path needs bf16, D in {HEAD_DIMS}, S * Hq / Hkv <= {MAX_QUERY_ROWS} "
+                         f"and 16-byte aligned caches (impl='sdpa' serves other shapes); got q {tuple(q.shape)} "
+                         f"{q.dtype}, caches {tuple(k_layer.shape)} {k_layer.dtype}")
+    lib = _native.load()
+    q = _aligned(q)
+    nchunks = -(-max_keys // int(lib.pto_decode_chunk()))
+    rows = B * S * hq * nchunks
+    ws = _partials(q.device, rows * (D + 2))
+    po, pm, pl = ws[:rows * D], ws[rows * D:rows * (D + 1)], ws[rows * (D + 1):rows * (D + 2)]
+    o = torch.empty_like(q)
+    _native.check(lib.pto_decode_attn_multi(q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), lens.data_ptr(),
+                                            o.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), B, S, max_len,
+                                            max_keys, hq, k_layer.shape[2], D, nchunks, _stream(q)),
+                  "decode_attn_multi")
     return o

@@ -5,6 +5,8 @@ usage: python tools/decode_bench.py [--batch 1,8] [--keys 512,2048,8192] [--head
                                     [--reps 200] [--json-out F]
        python tools/decode_bench.py --e2e [--model llama3-1b,llama3-8b] [--batch 1,8] [--prompt 128] [--tokens 128]
                                     [--decode-linear lib,hip,hip-fp8]
+       python tools/decode_bench.py --queries 2,4 [--batch 1,8] [--keys 512,2048,8192] [--head-dim 64,128]
+       python tools/decode_bench.py --e2e --queries 2,4 [--model llama3-1b,llama3-8b] [--batch 1,2,4,8] [--prompt 128]
        python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200] [--decode-linear hip-fp8,hip,lib]
                                              [--fp8-tiles 1,2,4]
 
@@ -28,6 +30,16 @@ and "hip" (the bf16 kernel) alternate, two runs each, over caches of equal shape
 bytes, the fp8 side's scales included, and the layers are sized so that the e4m3 caches alone exceed 512 MiB.
 --e2e --kv fp8: ``Llama.generate`` with ``kv_dtype=torch.float8_e4m3fn`` against the bf16 cache, with the peak of
 ``torch.cuda.max_memory_allocated`` per side ("*_peak_mb").
+
+--queries S,..: the multi-query kernel of ``csrc/kernels/decode_attention_multi.hip``.  Kernel mode: one
+``attend_rows`` call over S queries per sequence ("rows") against S back-to-back ``decode_attention`` calls over the
+same cache ("single", the S calls counted as one) and against ``attend_rows(impl="sdpa")`` ("sdpa"), alternating, two
+runs each, with the layers and the host's issue time as above; "rows_vs_single" is the ratio of the best device
+times.  --e2e --queries: one ``Llama.decode_steps`` over S tokens per sequence against one ``decode_step``, ms per
+step on a cache of --prompt rows (the lengths are put back before every step), for every --batch with B * S <= 16,
+projections by --decode-linear's first side (default hip); "steps_vs_step" is what S tokens cost relative to one.
+That ratio is the result: the models are randomly initialised, so how many drafted tokens a target would accept,
+and with it any speculative tokens/s, means nothing here and is not reported.
 
 --linear: ``ops.skinny.linear_rows`` against ``F.linear`` (+ ``swiglu_packed`` for w13) on the same tensors, at
 the five projection shapes of llama3-8b and llama3-1b and M = --rows.  The calls cycle through enough copies
@@ -132,6 +144,95 @@ def kernel_bench(a):
                 print(json.dumps(row), flush=True)
                 out.append(row)
                 del cache
+    return out
+
+
+def queries_bench(a):
+    from pytorch_operator_amd.ops.decode import KVCache, attend_rows, decode_attention
+    out = []
+    for D in a.head_dim:
+        for B in a.batch:
+            for n in a.keys:
+                per_layer = 2 * B * n * a.hkv * D * 2
+                L = max(1, min(64, -(-(512 << 20) // per_layer)))
+                cache = KVCache(L, B, n, a.hkv, D, torch.bfloat16, "cuda")
+                cache.k.normal_()
+                cache.v.normal_()
+                lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+                for S in a.queries:
+                    if S * (a.hq // a.hkv) > 16:
+                        continue
+                    q = torch.randn(B, S, a.hq, D, device="cuda").to(torch.bfloat16)
+                    qs = [q[:, s].contiguous() for s in range(S)]
+
+                    def single(i):
+                        for s in range(S):
+                            decode_attention(qs[s], cache.k[i], cache.v[i], lens)
+                    fns = {"rows": lambda i: attend_rows(q, cache.k[i], cache.v[i], lens), "single": single,
+                           "sdpa": lambda i: attend_rows(q, cache.k[i], cache.v[i], lens, impl="sdpa")}
+                    row = {"B": B, "n": n, "S": S, "Hq": a.hq, "Hkv": a.hkv, "D": D, "layers": L,
+                           "footprint_mb": round(L * per_layer / 1e6, 1)}
+                    for name in ("rows", "single", "sdpa") * 2:
+                        dev_us, host_us = timed(fns[name], L, a.reps)
+                        row.setdefault(name + "_us", []).append(round(dev_us, 2))
+                        row.setdefault(name + "_host_us", []).append(round(host_us, 2))
+                    row["rows_gbps"] = round(per_layer / min(row["rows_us"]) / 1e3, 1)
+                    row["rows_vs_single"] = round(min(row["rows_us"]) / min(row["single_us"]), 3)
+                    print(json.dumps(row), flush=True)
+                    out.append(row)
+                del cache
+    return out
+
+
+def steps_bench(a):
+    """ms per step: one ``decode_steps`` over S tokens per sequence against one ``decode_step``."""
+    from pytorch_operator_amd.models.llama import CONFIGS, Attention, Llama, TNLinear
+    from pytorch_operator_amd.ops.optim import to_bf16_matmul_weights
+    out = []
+    for name in a.model:
+        torch.manual_seed(0)
+        with torch.device("cuda"):
+            model = Llama(CONFIGS[name]).eval()
+        to_bf16_matmul_weights(model)
+        for p in model.parameters():
+            if hasattr(p, "_pto_master"):
+                del p._pto_master
+        V, n_layers = model.cfg.vocab_size, model.cfg.n_layers
+        for S in a.queries:
+            for B in [b for b in a.batch if b * S <= 16]:
+                prompts = torch.randint(0, V, (B, a.prompt), device="cuda")
+                toks = torch.randint(0, V, (B, S), device="cuda")
+                row = {"model": name, "B": B, "S": S, "keys": a.prompt, "linear": (a.decode_linear or ["hip"])[0]}
+                TNLinear.rows_impl = row["linear"]
+                try:
+                    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                        cache = model.new_cache(B, a.prompt + S)
+                        lens0 = torch.full((B,), a.prompt, dtype=torch.int32, device="cuda")
+                        model.prefill(prompts, lens0, cache)
+
+                        def step(i):
+                            cache.lens = lens0
+                            model.decode_step(toks[:, 0], cache)
+
+                        def steps(i):
+                            cache.lens = lens0
+                            model.decode_steps(toks, cache)
+                        Attention.decode_calls.clear()
+                        for side, fn in (("step", step), ("steps", steps)) * 2:
+                            dev_us, host_us = timed(fn, 1, a.reps)
+                            row.setdefault(side + "_ms", []).append(round(dev_us / 1e3, 3))
+                            row.setdefault(side + "_host_ms", []).append(round(host_us / 1e3, 3))
+                finally:
+                    TNLinear.rows_impl = "lib"
+                # both sides ran the HIP attention: 2 runs of (1 warm-up + reps) steps over every layer, each
+                assert dict(Attention.decode_calls) == {"hip": 2 * (a.reps + 1) * n_layers,
+                                                        "hip-rows": 2 * (a.reps + 1) * n_layers}, Attention.decode_calls
+                row["steps_vs_step"] = round(min(row["steps_ms"]) / min(row["step_ms"]), 3)
+                print(json.dumps(row), flush=True)
+                out.append(row)
+                del cache
+        del model
+        torch.cuda.empty_cache()
     return out
 
 
@@ -300,6 +401,9 @@ def main():
     p.add_argument("--fp8-tiles", type=ints, default=[], help="--linear with hip-fp8: also each forced tile count")
     p.add_argument("--kv", choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the e4m3 KV cache against the bf16 one (kernel mode and --e2e without --decode-linear)")
+    p.add_argument("--queries", type=ints, default=[],
+                   help="S, ..: the multi-query kernel against S single-query calls (kernel mode), or with --e2e one "
+                        "decode_steps over S tokens against one decode_step")
     p.add_argument("--json-out", default=None)
     a = p.parse_args()
     if not torch.cuda.is_available():
@@ -310,7 +414,11 @@ def main():
         p.error("--kv fp8 goes with the kernel mode or the attention --e2e")
     if set(a.fp8_tiles) - {1, 2, 4}:
         p.error("--fp8-tiles takes 1, 2 and / or 4")
-    if a.linear:
+    if a.queries and (a.linear or a.kv == "fp8" or min(a.queries) < 1):
+        p.error("--queries takes positive counts, in the kernel mode or with --e2e, on the bf16 cache")
+    if a.queries:
+        res = {"steps": steps_bench(a)} if a.e2e else {"queries": queries_bench(a)}
+    elif a.linear:
         res = {"linear": linear_bench(a)}
     elif a.e2e:
         res = {"e2e_linear": e2e_linear_bench(a)} if a.decode_linear else {"e2e": e2e_bench(a)}
