@@ -42,13 +42,11 @@
 //             of them accumulators), one workgroup per CU; with E = 8 every instance has no scratch, at
 //             most 140 registers and three workgroups per CU (profiles/decode_fp8/README.md has the table).
 //             Two head passes at G = 8 were not built.
-#include "decode_common.h"
+#include "decode_fp8.h"  // head_quantize, widen, scales_ok
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 using pto::f32x4;
 
@@ -58,30 +56,6 @@ constexpr int kTiles = 4;  // 16-key tiles per wave: kChunk / 16 / (kT / 64)
 using V8 = pto::Vec<8>;
 using pto::vload;
 using pto::vstore;
-
-// ---------------------------------------------------------------------------- the quantiser
-// x: this thread's 8 values of a head's row, already bf16 values; lpg = D / 8 consecutive lanes hold the
-// row.  Every lane of the group must be active.  Stores 8 e4m3 bytes at dst and, from the group's first
-// lane, the scale at sdst.
-__device__ __forceinline__ void head_quantize(const float (&x)[8], int lpg, bool first, uint8_t* dst, float* sdst) {
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(x[i]));
-  for (int o = lpg >> 1; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  const uint32_t u = __float_as_uint(amax);
-  // amax = m 2^e: e - 8, or e - 7 when m > 1.75 (a bf16's fraction is the top 7 of the 23 bits);
-  // a subnormal amax (exponent field 0) falls below the clamp either way
-  int se = (int)(u >> 23) - 127 - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
-  se = se < -126 ? -126 : se;
-  if (amax == 0.f) se = 0;
-  const float inv = __uint_as_float((uint32_t)(127 - se) << 23);  // 2^-se, exponent in [6, 253]
-  uint32_t lo = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv, x[1] * inv, 0, false);
-  lo = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[2] * inv, x[3] * inv, (int)lo, true);
-  uint32_t hi = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[4] * inv, x[5] * inv, 0, false);
-  hi = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[6] * inv, x[7] * inv, (int)hi, true);
-  *reinterpret_cast<u32x2*>(dst) = u32x2{lo, hi};
-  if (first) *sdst = __uint_as_float((uint32_t)(127 + se) << 23);
-}
 
 // ---------------------------------------------------------------------------- rope_append_fp8
 // One thread per 8-element group of the packed row; heads [0, Hq) -> q, [Hq, Hq+Hkv) -> k cache,
@@ -165,16 +139,6 @@ __global__ __launch_bounds__(kT) void kv_quantize_kernel(const uint16_t* __restr
 __device__ __forceinline__ f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
                                                  0, 0, 0);
-}
-
-// Eight e4m3 bytes (two dwords, k ascending) -> eight bf16 (an A fragment), exactly.
-__device__ __forceinline__ u32x4 widen(uint32_t lo, uint32_t hi) {
-  u32x4 a;
-  a[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
-  a[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
-  a[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
-  a[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
-  return a;
 }
 
 // W dwords of e4m3 (4 bytes each, ascending) -> 4 W floats.
@@ -393,10 +357,6 @@ int launch_decode_g(int G, const AttnArgs& a) {
     default: return -1;
   }
   return (int)hipGetLastError();
-}
-
-bool scales_ok(const void* ks, const void* vs, int sstride, int max_len) {
-  return sstride >= max_len && sstride % 4 == 0 && aligned16(ks) && aligned16(vs);
 }
 
 }  // namespace

@@ -201,7 +201,7 @@ class Attention(nn.Module):
     head dim 64 or 128, ...), the library's ``scaled_dot_product_attention`` otherwise -- an fp32 model
     called without autocast, for instance, runs the library path on a GPU without an error (the
     ``ops`` wrappers themselves never fall back).  ``decode_calls`` counts the decode steps per path
-    ("hip", "hip-fp8" on an e4m3 cache, "hip-rows" for a multi-token step, "sdpa", "cpu"), so that a benchmark
+    ("hip", "hip-fp8" on an e4m3 cache, "hip-rows" / "hip-rows-fp8" for a multi-token step, "sdpa", "cpu"), so that a benchmark
     or a test can assert which one it ran."""
 
     impl = "auto"  # "auto": HIP flash attention where it applies; "sdpa": library kernels
@@ -239,10 +239,15 @@ class Attention(nn.Module):
         if cache is not None and cache.pos is not None:
             # S tokens per sequence appended at pos .. pos + S - 1, each attending to the rows up to its own
             from ..ops import decode as Dc
-            q = Dc.append_rows(self.wqkv(x), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv)
-            hip = (self.decode_impl or self.impl) != "sdpa" and (not q.is_cuda or Dc.rows_supported(q, cache.k, cache.v))
-            Attention.decode_calls["cpu" if not q.is_cuda else ("hip-rows" if hip else "sdpa")] += 1
-            o = Dc.attend_rows(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa")
+            fp8 = cache.k.dtype == Dc.FP8  # one path per device, as in the S == 1 branch
+            q = Dc.append_rows(self.wqkv(x), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv,
+                               cache.k_scale, cache.v_scale)
+            hip = fp8 or ((self.decode_impl or self.impl) != "sdpa"
+                          and (not q.is_cuda or Dc.rows_supported(q, cache.k, cache.v)))
+            Attention.decode_calls["cpu" if not q.is_cuda else
+                                   (("hip-rows-fp8" if fp8 else "hip-rows") if hip else "sdpa")] += 1
+            o = Dc.attend_rows(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
+                               cache.k_scale, cache.v_scale)
             return self.wo(o.reshape(B, S, self.nh * self.hd))
         q, k, v = rope_qkv(self.wqkv(x), cos, sin, self.nh, self.nkv)
         if cache is not None:
@@ -436,8 +441,9 @@ class Llama(nn.Module):
         """Append S tokens per row (``tokens`` [B, S]) at positions ``cache.lens`` .. ``+ S - 1`` in one step
         and return the logits [B, S, V] after each of them: token s attends to the cache rows up to its own.
         ``cache.lens`` grows by S; ``max_keys`` bounds the lengths after the append, as in ``decode_step``.
-        The multi-query kernels of ``ops.decode`` take S * n_heads / n_kv_heads <= 16 on a bf16 cache (the
-        library path serves the rest); the projections take ``rows_linear``'s choice for B * S rows."""
+        The multi-query kernels of ``ops.decode`` take S * n_heads / n_kv_heads <= 16 on a bf16 or an e4m3 cache
+        (the library path serves the rest on a bf16 cache; on an e4m3 cache a larger S is an error); the
+        projections take ``rows_linear``'s choice for B * S rows."""
         if tokens.dim() != 2 or tokens.shape[1] < 1:
             raise ValueError(f"decode_steps: tokens must be [B, S] with S >= 1, got {tuple(tokens.shape)}")
         pos = cache.lens
@@ -520,7 +526,10 @@ class Llama(nn.Module):
         ``draft`` (another ``Llama`` with the same vocabulary, on the same device) and ``draft_tokens`` = k >= 1:
         greedy speculative decoding, see ``_speculate``.  The tokens are the target's own greedy choices, each
         the argmax of the logits returned for it; a round costs one multi-token target step and k + 1 draft
-        steps, and one host read.  The caches hold up to P + max_new_tokens + k rows."""
+        steps, and one host read.  The caches hold up to P + max_new_tokens + k rows.  With
+        ``kv_dtype=torch.float8_e4m3fn`` both caches are e4m3 and the verification step runs ``ops.decode``'s
+        e4m3 multi-token kernels ((k + 1) * n_heads / n_kv_heads <= 16); a rolled-back row's codes and scales
+        are dead like the row itself and are overwritten together."""
         V = self.cfg.vocab_size
         if not isinstance(prompts, torch.Tensor) or prompts.dim() != 2 or prompts.dtype != torch.long or \
                 prompts.shape[1] < 1:
@@ -544,8 +553,6 @@ class Llama(nn.Module):
                                  f"draft_tokens >= 1, got {type(draft).__name__} and {k!r}")
             if temperature > 0.0:
                 raise ValueError("generate: a draft model goes with greedy decoding (temperature 0)")
-            if kv_dtype == torch.float8_e4m3fn:
-                raise ValueError("generate: the multi-token step of a draft round has no e4m3 cache path")
             if draft.tok_embeddings.weight.device != self.tok_embeddings.weight.device:
                 raise ValueError("generate: draft and target must be on one device")
         max_len = P + T + k if max_len is None else max_len  # a draft round may write k rows past the last token

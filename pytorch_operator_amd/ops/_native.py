@@ -208,6 +208,9 @@ _SIGNATURES = {
     # decode_attention_multi.hip
     "pto_rope_append_multi": [_VP] * 7 + [_L] + [_I] * 7 + [_VP],
     "pto_decode_attn_multi": [_VP] * 8 + [_I] * 8 + [_VP],
+    # decode_attention_multi_fp8.hip
+    "pto_rope_append_multi_fp8": [_VP] * 6 + [_I] + [_VP] * 3 + [_L] + [_I] * 7 + [_VP],
+    "pto_decode_attn_multi_fp8": [_VP] * 5 + [_I] + [_VP] * 5 + [_I] * 8 + [_VP],
     # skinny_gemm.hip
     "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     # skinny_gemm_fp8.hip

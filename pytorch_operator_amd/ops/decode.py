@@ -24,8 +24,9 @@ the bf16 row the bf16 cache would hold.  ``rope_append`` and ``decode_attention`
 bf16: the attention is the bf16 attention on the dequantised cache.  q stays bf16; ``impl="sdpa"`` does not
 serve an FP8 cache.
 
-``append_rows`` / ``attend_rows`` (``csrc/kernels/decode_attention_multi.hip``) are the same two steps for S tokens
-per sequence; see the end of this file.
+``append_rows`` / ``attend_rows`` (``csrc/kernels/decode_attention_multi.hip``, and
+``decode_attention_multi_fp8.hip`` on an FP8 cache) are the same two steps for S tokens per sequence; see the end
+of this file.
 """
 from __future__ import annotations
 
@@ -335,8 +336,11 @@ def decode_attention(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tens
 # the cache stores nothing, token by token).  ``attend_rows`` is ``decode_attention`` for q [B, S, Hq, D]: query s
 # sees the keys j < n_s, n_s = min(lens[b], max_keys) - (S - 1 - s), ``lens`` counting the rows after the append;
 # n_s <= 0 gives a zero row.  The HIP kernel takes the S * Hq / Hkv query rows of a kv head as the 16 columns of
-# one MFMA tile: bf16, D in HEAD_DIMS, S * Hq / Hkv <= MAX_QUERY_ROWS; ``impl="sdpa"`` serves the rest.  The e4m3
-# cache has no multi-token path.
+# one MFMA tile: bf16, D in HEAD_DIMS, S * Hq / Hkv <= MAX_QUERY_ROWS; ``impl="sdpa"`` serves the rest.
+# An e4m3 cache (csrc/kernels/decode_attention_multi_fp8.hip) takes the layer's scales as ``k_scale`` / ``v_scale``,
+# as ``rope_append`` and ``decode_attention`` do: the append stores byte for byte what S calls of ``rope_append``
+# store, the attention is the bf16 one on the dequantised cache with both products on the MFMA, under the same
+# shape limits; ``impl="sdpa"`` does not serve it.
 MAX_QUERY_ROWS = 16
 
 
@@ -345,8 +349,10 @@ def _row_lens(lens, max_keys: int, S: int, s: int) -> torch.Tensor:
 
 
 def append_rows(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_layer: torch.Tensor,
-                v_layer: torch.Tensor, pos: torch.Tensor, hq: int, hkv: int) -> torch.Tensor:
-    """q [B, S, hq, D], token s rotated at ``pos[b] + s``; its k (rotated) and v go to that cache row in place."""
+                v_layer: torch.Tensor, pos: torch.Tensor, hq: int, hkv: int,
+                k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q [B, S, hq, D], token s rotated at ``pos[b] + s``; its k (rotated) and v go to that cache row in place --
+    quantised, with their scales to ``k_scale`` / ``v_scale`` [B, hkv, max_len_pad], when the cache is e4m3."""
     if qkv.dim() != 3 or hq <= 0 or hkv <= 0 or qkv.shape[1] < 1 or qkv.shape[2] % (hq + 2 * hkv):
         raise ValueError(f"append_rows: qkv must be [B, S, (hq + 2 hkv) * D]; got {tuple(qkv.shape)} hq {hq} hkv {hkv}")
     B, S, W = qkv.shape
@@ -355,12 +361,19 @@ def append_rows(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, k_layer
     _check_index("append_rows", "pos", pos, B, qkv.device)
     if D % 8 or cos.dim() != 2 or cos.shape[1] != D // 2 or cos.shape != sin.shape or cos.shape[0] < 1:
         raise ValueError(f"append_rows: D % 8 == 0 and tables [rows, D/2]; got D {D}, cos {tuple(cos.shape)}")
-    if k_layer.dtype == FP8:
-        raise ValueError("append_rows: an e4m3 cache takes one token per step (rope_append); S tokens need a bf16 "
-                         "or fp32 cache")
+    fp8 = _check_scales("append_rows", k_layer, k_scale, v_scale)
     if not qkv.is_cuda:
-        return torch.stack([rope_append_reference(qkv[:, s], cos, sin, k_layer, v_layer, pos + s, hq, hkv)
-                            for s in range(S)], dim=1)
+        return torch.stack([rope_append_reference(qkv[:, s], cos, sin, k_layer, v_layer, pos + s, hq, hkv,
+                                                  k_scale, v_scale) for s in range(S)], dim=1)
+    if fp8:
+        _fp8_hip_ok("append_rows", qkv, k_layer, v_layer, k_scale, v_scale, D)
+        qkv, cos, sin = _aligned(qkv), _aligned(cos.float()), _aligned(sin.float())
+        q = qkv.new_empty(B, S, hq, D)
+        _native.check(_native.load().pto_rope_append_multi_fp8(
+            qkv.data_ptr(), q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), k_scale.data_ptr(),
+            v_scale.data_ptr(), k_scale.shape[2], cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), B, S,
+            k_layer.shape[1], cos.shape[0], hq, hkv, D, _DT[qkv.dtype], _stream(qkv)), "rope_append_multi_fp8")
+        return q
     if qkv.dtype not in _DT or k_layer.dtype != qkv.dtype or k_layer.data_ptr() % 16 or v_layer.data_ptr() % 16:
         raise ValueError(f"append_rows: qkv and the caches must share fp32 or bf16 and be 16-byte aligned; got "
                          f"{qkv.dtype}, {k_layer.dtype}")
@@ -397,14 +410,16 @@ def rows_supported(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor
         return False
     B, S, hq, D = q.shape
     hkv = k_layer.shape[2]
-    return (q.dtype == torch.bfloat16 and k_layer.dtype == torch.bfloat16 and v_layer.dtype == torch.bfloat16
+    return (q.dtype == torch.bfloat16 and k_layer.dtype == v_layer.dtype and k_layer.dtype in (torch.bfloat16, FP8)
             and D in HEAD_DIMS and hkv > 0 and S >= 1 and hq % hkv == 0 and S * (hq // hkv) <= MAX_QUERY_ROWS
             and B <= 65535 and hkv <= 65535)
 
 
 def attend_rows(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor, lens: torch.Tensor,
-                max_keys: Optional[int] = None, impl: str = "auto") -> torch.Tensor:
-    """o [B, S, Hq, D]: query s of sequence b over the first n_s = min(lens[b], max_keys) - (S - 1 - s) cache rows."""
+                max_keys: Optional[int] = None, impl: str = "auto",
+                k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """o [B, S, Hq, D]: query s of sequence b over the first n_s = min(lens[b], max_keys) - (S - 1 - s) cache rows;
+    ``k_scale`` / ``v_scale`` are the layer's scales when the cache is e4m3."""
     if impl not in ("auto", "sdpa"):
         raise ValueError(f"attend_rows: impl must be 'auto' or 'sdpa', got {impl!r}")
     if q.dim() != 4 or k_layer.dim() != 4 or k_layer.shape[2] <= 0 or q.shape[1] < 1 or \
@@ -419,19 +434,25 @@ def attend_rows(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor, l
         max_keys = max_len
     if not isinstance(max_keys, int) or not 1 <= max_keys <= max_len:
         raise ValueError(f"attend_rows: max_keys must be an int in [1, max_len = {max_len}], got {max_keys!r}")
-    if k_layer.dtype == FP8:
-        raise ValueError("attend_rows: an e4m3 cache takes one query per step (decode_attention)")
-    if q.dtype != k_layer.dtype:
+    fp8 = _check_scales("attend_rows", k_layer, k_scale, v_scale)
+    if fp8 and impl == "sdpa":
+        raise ValueError("attend_rows: impl='sdpa' does not serve an e4m3 cache (the library path needs q and the "
+                         "cache in one dtype)")
+    if not fp8 and q.dtype != k_layer.dtype:
         raise ValueError(f"attend_rows: q and the caches must share a dtype; got {q.dtype}, {k_layer.dtype}")
     if not q.is_cuda:
+        if fp8:  # rows past the lengths may hold anything, NaN codes and scales included: selection hides them
+            k_layer, v_layer = dequantize_cache(k_layer, k_scale, q.dtype), dequantize_cache(v_layer, v_scale, q.dtype)
         return torch.stack([decode_attention_reference(q[:, s], k_layer, v_layer, _row_lens(lens, max_keys, S, s),
                                                        max_keys) for s in range(S)], dim=1)
     if impl == "sdpa":
         return attend_rows_sdpa(q, k_layer, v_layer, lens, max_keys)
     if not rows_supported(q, k_layer, v_layer) or k_layer.data_ptr() % 16 or v_layer.data_ptr() % 16:
-        raise ValueError(f"attend_rows: the HIP path needs bf16, D in {HEAD_DIMS}, S * Hq / Hkv <= {MAX_QUERY_ROWS} "
-                         f"and 16-byte aligned caches (impl='sdpa' serves other shapes); got q {tuple(q.shape)} "
-                         f"{q.dtype}, caches {tuple(k_layer.shape)} {k_layer.dtype}")
+        raise ValueError(f"attend_rows: the HIP path needs bf16 (or a bf16 q with e4m3 caches), D in {HEAD_DIMS}, "
+                         f"S * Hq / Hkv <= {MAX_QUERY_ROWS} and 16-byte aligned caches (impl='sdpa' serves other "
+                         f"bf16 shapes); got q {tuple(q.shape)} {q.dtype}, caches {tuple(k_layer.shape)} {k_layer.dtype}")
+    if fp8:
+        _fp8_hip_ok("attend_rows", q, k_layer, v_layer, k_scale, v_scale, D)
     lib = _native.load()
     q = _aligned(q)
     nchunks = -(-max_keys // int(lib.pto_decode_chunk()))
@@ -439,6 +460,12 @@ def attend_rows(q: torch.Tensor, k_layer: torch.Tensor, v_layer: torch.Tensor, l
     ws = _partials(q.device, rows * (D + 2))
     po, pm, pl = ws[:rows * D], ws[rows * D:rows * (D + 1)], ws[rows * (D + 1):rows * (D + 2)]
     o = torch.empty_like(q)
+    if fp8:
+        _native.check(lib.pto_decode_attn_multi_fp8(
+            q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+            k_scale.shape[2], lens.data_ptr(), o.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), B, S,
+            max_len, max_keys, hq, k_layer.shape[2], D, nchunks, _stream(q)), "decode_attn_multi_fp8")
+        return o
     _native.check(lib.pto_decode_attn_multi(q.data_ptr(), k_layer.data_ptr(), v_layer.data_ptr(), lens.data_ptr(),
                                             o.data_ptr(), po.data_ptr(), pm.data_ptr(), pl.data_ptr(), B, S, max_len,
                                             max_keys, hq, k_layer.shape[2], D, nchunks, _stream(q)),

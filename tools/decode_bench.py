@@ -7,6 +7,7 @@ usage: python tools/decode_bench.py [--batch 1,8] [--keys 512,2048,8192] [--head
                                     [--decode-linear lib,hip,hip-fp8]
        python tools/decode_bench.py --queries 2,4 [--batch 1,8] [--keys 512,2048,8192] [--head-dim 64,128]
        python tools/decode_bench.py --e2e --queries 2,4 [--model llama3-1b,llama3-8b] [--batch 1,2,4,8] [--prompt 128]
+       python tools/decode_bench.py --queries 1,2,4 --kv fp8 [--e2e] [...]
        python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200] [--decode-linear hip-fp8,hip,lib]
                                              [--fp8-tiles 1,2,4]
 
@@ -40,6 +41,13 @@ step on a cache of --prompt rows (the lengths are put back before every step), f
 projections by --decode-linear's first side (default hip); "steps_vs_step" is what S tokens cost relative to one.
 That ratio is the result: the models are randomly initialised, so how many drafted tokens a target would accept,
 and with it any speculative tokens/s, means nothing here and is not reported.
+
+--queries S,.. --kv fp8: the e4m3 multi-query kernel of ``csrc/kernels/decode_attention_multi_fp8.hip``.  Kernel
+mode, three sides alternating, two runs each: one e4m3 ``attend_rows`` call ("rows8"), S back-to-back e4m3
+``decode_attention`` calls ("single8") and the bf16 ``attend_rows`` call over a bf16 cache of the same shape
+("rows"); layers as with --kv fp8 alone, "rows8_gbps" counts the e4m3 side's own bytes, scales included;
+"rows8_vs_single8" and "rows8_vs_rows" are ratios of the best device times.  With --e2e: ``decode_steps`` against
+``decode_step`` as above, both on an e4m3 cache.
 
 --linear: ``ops.skinny.linear_rows`` against ``F.linear`` (+ ``swiglu_packed`` for w13) on the same tensors, at
 the five projection shapes of llama3-8b and llama3-1b and M = --rows.  The calls cycle through enough copies
@@ -184,6 +192,50 @@ def queries_bench(a):
     return out
 
 
+def queries_fp8_bench(a):
+    from pytorch_operator_amd.ops.decode import FP8, KVCache, attend_rows, decode_attention, quantize_kv
+    out = []
+    for D in a.head_dim:
+        for B in a.batch:
+            for n in a.keys:
+                own = {"rows": 2 * B * n * a.hkv * D * 2, "rows8": 2 * B * n * a.hkv * (D + 4)}
+                L = max(1, min(64, -(-(512 << 20) // own["rows8"])))
+                cache, cache8 = KVCache(L, B, n, a.hkv, D, torch.bfloat16, "cuda"), KVCache(L, B, n, a.hkv, D, FP8, "cuda")
+                for i in range(L):
+                    cache.k[i].normal_()
+                    cache.v[i].normal_()
+                    quantize_kv(cache.k[i], cache.v[i], cache8.k[i], cache8.v[i], cache8.k_scale[i], cache8.v_scale[i])
+                lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+                for S in a.queries:
+                    if S * (a.hq // a.hkv) > 16:
+                        continue
+                    q = torch.randn(B, S, a.hq, D, device="cuda").to(torch.bfloat16)
+                    qs = [q[:, s].contiguous() for s in range(S)]
+
+                    def single8(i):
+                        for s in range(S):
+                            decode_attention(qs[s], cache8.k[i], cache8.v[i], lens, k_scale=cache8.k_scale[i],
+                                             v_scale=cache8.v_scale[i])
+                    fns = {"rows8": lambda i: attend_rows(q, cache8.k[i], cache8.v[i], lens, k_scale=cache8.k_scale[i],
+                                                          v_scale=cache8.v_scale[i]),
+                           "single8": single8, "rows": lambda i: attend_rows(q, cache.k[i], cache.v[i], lens)}
+                    row = {"B": B, "n": n, "S": S, "Hq": a.hq, "Hkv": a.hkv, "D": D, "layers": L,
+                           "footprint_mb": round(L * own["rows"] / 1e6, 1),
+                           "fp8_footprint_mb": round(L * own["rows8"] / 1e6, 1)}
+                    for name in ("rows8", "single8", "rows") * 2:
+                        dev_us, host_us = timed(fns[name], L, a.reps)
+                        row.setdefault(name + "_us", []).append(round(dev_us, 2))
+                        row.setdefault(name + "_host_us", []).append(round(host_us, 2))
+                    for name in ("rows8", "rows"):
+                        row[name + "_gbps"] = round(own[name] / min(row[name + "_us"]) / 1e3, 1)
+                    row["rows8_vs_single8"] = round(min(row["rows8_us"]) / min(row["single8_us"]), 3)
+                    row["rows8_vs_rows"] = round(min(row["rows8_us"]) / min(row["rows_us"]), 3)
+                    print(json.dumps(row), flush=True)
+                    out.append(row)
+                del cache, cache8
+    return out
+
+
 def steps_bench(a):
     """ms per step: one ``decode_steps`` over S tokens per sequence against one ``decode_step``."""
     from pytorch_operator_amd.models.llama import CONFIGS, Attention, Llama, TNLinear
@@ -202,11 +254,12 @@ def steps_bench(a):
             for B in [b for b in a.batch if b * S <= 16]:
                 prompts = torch.randint(0, V, (B, a.prompt), device="cuda")
                 toks = torch.randint(0, V, (B, S), device="cuda")
-                row = {"model": name, "B": B, "S": S, "keys": a.prompt, "linear": (a.decode_linear or ["hip"])[0]}
+                row = {"model": name, "B": B, "S": S, "keys": a.prompt, "linear": (a.decode_linear or ["hip"])[0],
+                       "kv": a.kv}
                 TNLinear.rows_impl = row["linear"]
                 try:
                     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-                        cache = model.new_cache(B, a.prompt + S)
+                        cache = model.new_cache(B, a.prompt + S, torch.float8_e4m3fn if a.kv == "fp8" else None)
                         lens0 = torch.full((B,), a.prompt, dtype=torch.int32, device="cuda")
                         model.prefill(prompts, lens0, cache)
 
@@ -225,8 +278,9 @@ def steps_bench(a):
                 finally:
                     TNLinear.rows_impl = "lib"
                 # both sides ran the HIP attention: 2 runs of (1 warm-up + reps) steps over every layer, each
-                assert dict(Attention.decode_calls) == {"hip": 2 * (a.reps + 1) * n_layers,
-                                                        "hip-rows": 2 * (a.reps + 1) * n_layers}, Attention.decode_calls
+                sfx = "-fp8" if a.kv == "fp8" else ""
+                assert dict(Attention.decode_calls) == {"hip" + sfx: 2 * (a.reps + 1) * n_layers,
+                                                        "hip-rows" + sfx: 2 * (a.reps + 1) * n_layers}, Attention.decode_calls
                 row["steps_vs_step"] = round(min(row["steps_ms"]) / min(row["step_ms"]), 3)
                 print(json.dumps(row), flush=True)
                 out.append(row)
@@ -400,7 +454,8 @@ def main():
                         "attention A/B); --linear: the sides in their order (default hip,lib)")
     p.add_argument("--fp8-tiles", type=ints, default=[], help="--linear with hip-fp8: also each forced tile count")
     p.add_argument("--kv", choices=["bf16", "fp8"], default="bf16",
-                   help="fp8: the e4m3 KV cache against the bf16 one (kernel mode and --e2e without --decode-linear)")
+                   help="fp8: the e4m3 KV cache against the bf16 one (kernel mode and --e2e without --decode-linear); with "
+                        "--queries: the e4m3 multi-query kernel")
     p.add_argument("--queries", type=ints, default=[],
                    help="S, ..: the multi-query kernel against S single-query calls (kernel mode), or with --e2e one "
                         "decode_steps over S tokens against one decode_step")
@@ -414,10 +469,12 @@ def main():
         p.error("--kv fp8 goes with the kernel mode or the attention --e2e")
     if set(a.fp8_tiles) - {1, 2, 4}:
         p.error("--fp8-tiles takes 1, 2 and / or 4")
-    if a.queries and (a.linear or a.kv == "fp8" or min(a.queries) < 1):
-        p.error("--queries takes positive counts, in the kernel mode or with --e2e, on the bf16 cache")
-    if a.queries:
-        res = {"steps": steps_bench(a)} if a.e2e else {"queries": queries_bench(a)}
+    if a.queries and (a.linear or min(a.queries) < 1):
+        p.error("--queries takes positive counts, in the kernel mode or with --e2e")
+    if a.queries and a.e2e:
+        res = {"steps": steps_bench(a)}
+    elif a.queries:
+        res = {"queries_fp8": queries_fp8_bench(a)} if a.kv == "fp8" else {"queries": queries_bench(a)}
     elif a.linear:
         res = {"linear": linear_bench(a)}
     elif a.e2e:
