@@ -189,6 +189,9 @@ def parse_args(argv=None):
     p.add_argument("--decode-linear", choices=["lib", "hip"], default="lib",
                    help="--sample-every: the decode step's projections and lm-head by the library GEMM, or by the "
                         "skinny HIP GEMM (csrc/kernels/skinny_gemm.hip) where the worker's weights are bf16")
+    p.add_argument("--decode-fuse-norm", action="store_true",
+                   help="--sample-every with --decode-linear hip: fold the decode step's residual adds and RMSNorms "
+                        "into the projections around them (csrc/kernels/skinny_gemm_fused.hip)")
     p.add_argument("--lr", type=float, default=None)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--json-out", default=None)
@@ -198,7 +201,8 @@ def parse_args(argv=None):
                                   ("--sample-prompt-len", args.sample_prompt_len, 16),
                                   ("--sample-temperature", args.sample_temperature, 0.0),
                                   ("--sample-top-k", args.sample_top_k, 0),
-                                  ("--decode-linear", args.decode_linear, "lib")) if v != d]
+                                  ("--decode-linear", args.decode_linear, "lib"),
+                                  ("--decode-fuse-norm", args.decode_fuse_norm, False)) if v != d]
     if sampling and not args.model.startswith("llama"):
         p.error(f"{sampling[0]} is for the Llama models")
     args.sample_prompt_ids = None
@@ -623,13 +627,14 @@ def main(argv=None) -> int:
         optimizer nor the gradients.  The KV cache lives for the call."""
         from ..models.llama import TNLinear
         was, TNLinear.rows_impl = TNLinear.rows_impl, args.decode_linear
+        was_fuse, TNLinear.rows_fuse_norm = TNLinear.rows_fuse_norm, args.decode_fuse_norm
         try:
             with amp:
                 toks = bare.generate(torch.tensor([prompt_ids], dtype=torch.long, device=dev),
                                      max_new_tokens=args.sample_tokens, temperature=args.sample_temperature,
                                      top_k=args.sample_top_k, generator=sample_gen)
         finally:
-            TNLinear.rows_impl = was
+            TNLinear.rows_impl, TNLinear.rows_fuse_norm = was, was_fuse
         if rank == 0:
             print(json.dumps({"event": "sample", "step": gstep, "prompt": prompt_ids, "tokens": toks[0].tolist()}),
                   flush=True)

@@ -36,6 +36,10 @@ def parse_args(argv=None):
                         "(csrc/kernels/skinny_gemm_fp8.hip; the weights are cast to bf16, quantised once and "
                         "overwritten with their dequantised values, so the model that runs is the quantised one "
                         "on both the prefill and the decode step)")
+    p.add_argument("--decode-fuse-norm", action="store_true",
+                   help="with --decode-linear hip or hip-fp8 on a GPU: fold the decode step's residual adds and "
+                        "RMSNorms into the projections around them (csrc/kernels/skinny_gemm_fused.hip): 7 launches "
+                        "per layer instead of 9")
     p.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the KV cache in e4m3 with a power-of-two scale per (token, kv head), written and read "
                         "by csrc/kernels/decode_attention_fp8.hip: half the cache bytes. It quantises k and v, so "
@@ -58,7 +62,7 @@ def main(argv=None) -> int:
         with torch.device(dev):
             model = Llama(cfg)
         step = train_ckpt.load_weights(args.ckpt_dir, model, dev)
-        TNLinear.rows_impl = args.decode_linear
+        TNLinear.rows_impl, TNLinear.rows_fuse_norm = args.decode_linear, args.decode_fuse_norm
         if args.decode_linear != "lib" and dev.type == "cuda":
             # once, here: the kernel takes bf16 weights as they lie, and a cast per call would cost more than it
             for mod in model.modules():

@@ -127,6 +127,11 @@ class TNLinear(nn.Linear):
     # leaves every call where it was
     rows_impl = "lib"
     rows_calls = collections.Counter()  # such calls per path ("hip", "hip-fp8", "lib") on a GPU
+    # True, with rows_impl "hip" or "hip-fp8": a decode step on a GPU folds its residual adds and RMSNorms
+    # into the projections around them (Llama._decode_fused; ops.skinny.linear_rows_add_norm /
+    # linear_rows_scaled), counted in rows_calls under rows_impl + "-add-norm" and + "-scaled", and the one
+    # norm launch left per step under "rms-norm".  A step outside those kernels' contract runs as before.
+    rows_fuse_norm = False
 
     def __init__(self, fin: int, fout: int):
         super().__init__(fin, fout, bias=False)
@@ -225,30 +230,8 @@ class Attention(nn.Module):
         B, S, _ = x.shape
         from ..ops import attention as A
         from ..ops.llm import rope_qkv
-        if cache is not None and S == 1:
-            from ..ops import decode as Dc
-            fp8 = cache.k.dtype == Dc.FP8  # the e4m3 cache has one path per device: no library side to fall to
-            q = Dc.rope_append(self.wqkv(x).reshape(B, -1), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv,
-                               cache.k_scale, cache.v_scale)
-            hip = fp8 or ((self.decode_impl or self.impl) != "sdpa"
-                          and (not q.is_cuda or Dc.hip_supported(q, cache.k, cache.v)))
-            Attention.decode_calls["cpu" if not q.is_cuda else (("hip-fp8" if fp8 else "hip") if hip else "sdpa")] += 1
-            o = Dc.decode_attention(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
-                                    cache.k_scale, cache.v_scale)
-            return self.wo(o.reshape(B, 1, self.nh * self.hd))
-        if cache is not None and cache.pos is not None:
-            # S tokens per sequence appended at pos .. pos + S - 1, each attending to the rows up to its own
-            from ..ops import decode as Dc
-            fp8 = cache.k.dtype == Dc.FP8  # one path per device, as in the S == 1 branch
-            q = Dc.append_rows(self.wqkv(x), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv,
-                               cache.k_scale, cache.v_scale)
-            hip = fp8 or ((self.decode_impl or self.impl) != "sdpa"
-                          and (not q.is_cuda or Dc.rows_supported(q, cache.k, cache.v)))
-            Attention.decode_calls["cpu" if not q.is_cuda else
-                                   (("hip-rows-fp8" if fp8 else "hip-rows") if hip else "sdpa")] += 1
-            o = Dc.attend_rows(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
-                               cache.k_scale, cache.v_scale)
-            return self.wo(o.reshape(B, S, self.nh * self.hd))
+        if cache is not None and (S == 1 or cache.pos is not None):
+            return self.wo(self.decode_heads(self.wqkv(x), cos, sin, cache))
         q, k, v = rope_qkv(self.wqkv(x), cos, sin, self.nh, self.nkv)
         if cache is not None:
             n = min(S, cache.k.shape[1])  # a prompt padded to the attention kernels' multiple may end past the cache
@@ -270,6 +253,32 @@ class Attention(nn.Module):
         else:
             o = A.sdpa_bshd(q, k, v, causal=True)
         return self.wo(o.reshape(B, S, self.nh * self.hd))
+
+    def decode_heads(self, qkv, cos, sin, cache):
+        """A decode step between the two projections: ``qkv`` [B, S, (Hq + 2 Hkv) D] (``wqkv``'s output) is
+        rotated, k and v are appended to the cache and the queries attend; returns [B, S, Hq D] for ``wo``."""
+        from ..ops import decode as Dc
+        B, S, _ = qkv.shape
+        fp8 = cache.k.dtype == Dc.FP8  # the e4m3 cache has one path per device: no library side to fall to
+        if S == 1:
+            q = Dc.rope_append(qkv.reshape(B, -1), cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv,
+                               cache.k_scale, cache.v_scale)
+            hip = fp8 or ((self.decode_impl or self.impl) != "sdpa"
+                          and (not q.is_cuda or Dc.hip_supported(q, cache.k, cache.v)))
+            Attention.decode_calls["cpu" if not q.is_cuda else (("hip-fp8" if fp8 else "hip") if hip else "sdpa")] += 1
+            o = Dc.decode_attention(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
+                                    cache.k_scale, cache.v_scale)
+        else:
+            # S tokens per sequence appended at pos .. pos + S - 1, each attending to the rows up to its own
+            q = Dc.append_rows(qkv, cos, sin, cache.k, cache.v, cache.pos, self.nh, self.nkv,
+                               cache.k_scale, cache.v_scale)
+            hip = fp8 or ((self.decode_impl or self.impl) != "sdpa"
+                          and (not q.is_cuda or Dc.rows_supported(q, cache.k, cache.v)))
+            Attention.decode_calls["cpu" if not q.is_cuda else
+                                   (("hip-rows-fp8" if fp8 else "hip-rows") if hip else "sdpa")] += 1
+            o = Dc.attend_rows(q, cache.k, cache.v, cache.lens, cache.max_keys, "auto" if hip else "sdpa",
+                               cache.k_scale, cache.v_scale)
+        return o.reshape(B, S, self.nh * self.hd)
 
 
 class FeedForward(nn.Module):
@@ -431,6 +440,10 @@ class Llama(nn.Module):
         mk = cache.max_len if max_keys is None else max_keys
         cos, sin = self._rope(cache, cache.max_len)
         h, d = self.tok_embeddings(tokens).unsqueeze(1), None
+        if self._fuse_norm(h):
+            logits = self._decode_fused(h, cos, sin, cache, pos, lens, mk)
+            cache.lens = lens
+            return logits[:, 0]
         for i, blk in enumerate(self.layers):
             h, d = blk(h, d, cos, sin, None, self._layer_cache(cache, i, pos, lens, mk))
         logits = self._lm_head(self.norm.add_forward(h, d)[1])
@@ -451,11 +464,93 @@ class Llama(nn.Module):
         mk = cache.max_len if max_keys is None else max_keys
         cos, sin = self._rope(cache, cache.max_len)
         h, d = self.tok_embeddings(tokens), None
+        if self._fuse_norm(h):
+            logits = self._decode_fused(h, cos, sin, cache, pos, lens, mk)
+            cache.lens = lens
+            return logits
         for i, blk in enumerate(self.layers):
             h, d = blk(h, d, cos, sin, None, self._layer_cache(cache, i, pos, lens, mk))
         logits = self._lm_head(self.norm.add_forward(h, d)[1])
         cache.lens = lens
         return logits
+
+    # ------------------------------------------------------------------ decode step with the norms folded in
+    def _fuse_norm(self, h: torch.Tensor) -> bool:
+        """Whether a decode step whose embedded tokens are ``h`` [B, S, dim] takes ``_decode_fused``: the switch
+        is on, ``rows_linear`` would send its projections to the skinny GEMMs, and every projection and norm of
+        the model is inside the fused kernels' contract (asked once per weight format and device, not per
+        step: the checks cost what the fusion saves).  Otherwise the step runs the existing path whole."""
+        from ..ops import skinny
+        impl = TNLinear.rows_impl
+        if not (TNLinear.rows_fuse_norm and h.is_cuda and impl in ("hip", "hip-fp8") and not torch.is_grad_enabled()
+                and h.numel() <= skinny.max_rows() * h.shape[-1]):
+            return False
+        if h.dtype != torch.bfloat16 and not (h.dtype == torch.float32 and torch.is_autocast_enabled("cuda")
+                                              and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+            return False
+        key = (impl, h.device, self.output.weight.dtype, getattr(self.output, "rows_q", None) is not None)
+        known = self.__dict__.setdefault("_fuse_norm_ok", {})
+        if key not in known:
+            known[key] = self._fuse_norm_contract(h.device)
+        return known[key]
+
+    def _fuse_norm_contract(self, device) -> bool:
+        from ..ops import skinny
+        fp8 = TNLinear.rows_impl == "hip-fp8"
+        probe = {}
+        mods = [(self.output, False)]
+        for blk in self.layers:
+            mods += [(blk.attention.wqkv, False), (blk.attention.wo, False), (blk.feed_forward.w13, True),
+                     (blk.feed_forward.w2, False)]
+        for mod, swiglu in mods:
+            K = mod.weight.shape[1]
+            x = probe.setdefault(K, torch.empty(1, K, dtype=torch.bfloat16, device=device))
+            if fp8:
+                if getattr(mod, "rows_q", None) is None:
+                    return False
+                if mod.rows_q.device != device:  # plain attributes do not follow Module.to(): once, here
+                    mod.rows_q, mod.rows_scale = mod.rows_q.to(device), mod.rows_scale.to(device)
+                if not skinny.hip_supported_fp8(x, mod.rows_q, mod.rows_scale, swiglu):
+                    return False
+            elif mod.weight.dtype != torch.bfloat16 or not skinny.hip_supported(x, mod.weight, swiglu):
+                return False
+        norms = [self.norm] + [n for blk in self.layers for n in (blk.attention_norm, blk.ffn_norm)]
+        return self.cfg.dim % skinny.SS_TILE == 0 and all(
+            n.weight.dtype == torch.float32 and n.weight.is_cuda and n.weight.is_contiguous() for n in norms)
+
+    def _decode_fused(self, h, cos, sin, cache, pos, lens, mk):
+        """The blocks and the lm-head of a decode step, carrying (h, a, ss) from one projection to the next:
+        h the residual stream, a = bf16(h * gamma) the next projection's operand, ss the partial sums of h^2
+        from which that projection takes rstd.  Each wo adds the residual and takes its block's ffn_norm
+        weight, each w2 the next block's attention_norm weight (the model's norm after the last block); wqkv,
+        w13 + SwiGLU and the lm-head scale by rstd.  The first block's attention_norm has no producer: a plain
+        norm and the plain GEMM.  7 launches per layer and 2 per step, against 9 and 2."""
+        from ..ops import skinny
+        from ..ops.llm import _aligned
+        impl, calls = TNLinear.rows_impl, TNLinear.rows_calls
+        L = len(self.layers)
+
+        def weight(mod):
+            return (mod.rows_q, mod.rows_scale) if impl == "hip-fp8" else (mod.weight, None)
+
+        h = _aligned(h)
+        a = self.layers[0].attention_norm(h).to(torch.bfloat16)
+        ss = None
+        calls["rms-norm"] += 1
+        for i, blk in enumerate(self.layers):
+            att, ffn = blk.attention, blk.feed_forward
+            if ss is None:
+                qkv = rows_linear(a, att.wqkv.weight, mod=att.wqkv)
+            else:
+                qkv = skinny.launch_scaled(a, *weight(att.wqkv), ss, blk.attention_norm.eps)
+            o = att.decode_heads(qkv, cos, sin, self._layer_cache(cache, i, pos, lens, mk))
+            h, a, ss = skinny.launch_add_norm(o, *weight(att.wo), h, blk.ffn_norm.weight)
+            y = skinny.launch_scaled(a, *weight(ffn.w13), ss, blk.ffn_norm.eps, swiglu=True)
+            nxt = self.layers[i + 1].attention_norm if i + 1 < L else self.norm
+            h, a, ss = skinny.launch_add_norm(y, *weight(ffn.w2), h, nxt.weight)
+        calls[impl + "-scaled"] += 2 * L
+        calls[impl + "-add-norm"] += 2 * L
+        return skinny.launch_scaled(a, *weight(self.output), ss, self.norm.eps)
 
     def _speculate(self, draft, k: int, prompts, lens, cache, T: int, eos_id, return_logits: bool):
         """The token loop of ``generate`` with a draft model (greedy).  A round: the draft takes k + 1 single

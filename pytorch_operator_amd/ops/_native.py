@@ -55,7 +55,8 @@ def _sources():
 # (MI355X_MICROARCH.md, constants table).
 # skinny_gemm_fp8.hip: no packed fp32 VALU ops (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): its reduce and
 # its scale multiply are fp32 vectors the compiler would pack, and the kernel's bit-identity claims rest on
-# plain fp32 arithmetic.
+# plain fp32 arithmetic.  skinny_gemm_fused.hip: the same, for the same reason (its accumulators are to be
+# the plain kernels' bit for bit, and its sums of squares have a stated order).
 # mnist_kernels.hip: kernel-argument preloading -- the command processor writes the leading 14
 # argument dwords into user SGPRs at wave launch, so the step kernels (whose parameter lists lead
 # with what their first loads need) start without a scalar-load round trip; firmware without the
@@ -64,7 +65,8 @@ _FILE_FLAGS = {"mnist_kernels.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16
                "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_d64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_bwd_pipe.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
-               "skinny_gemm_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+               "skinny_gemm_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "skinny_gemm_fused.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _source_digest() -> str:
@@ -215,6 +217,11 @@ _SIGNATURES = {
     "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     # skinny_gemm_fp8.hip
     "pto_skinny_fp8_gemm": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP],
+    # skinny_gemm_fused.hip
+    "pto_skinny_add_norm": [_VP] * 7 + [_I, _I, _I, _I, _VP],
+    "pto_skinny_fp8_add_norm": [_VP] * 8 + [_I, _I, _I, _I, _I, _VP],
+    "pto_skinny_scaled": [_VP, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP],
+    "pto_skinny_fp8_scaled": [_VP, _VP, _VP, _VP, _F, _VP, _I, _I, _I, _I, _I, _VP],
     # adamw.hip
     "pto_adamw_step_scaled": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP],
     "pto_adamw_step_clipped": [_VP, _VP, _VP, _VP, _VP, _L, _I, _F, _F, _F, _F, _F, _I, _F, _VP, _F, _VP],
@@ -262,7 +269,8 @@ _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_
              "pto_graph_nodes": [_VP], "pto_grad_sumsq_parts": [_L, _I], "pto_fp8_amax_parts": [_L],
              "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": [], "pto_decode_multi_rows": [],
              "pto_skinny_max_rows": [], "pto_skinny_waves": [_I],
-             "pto_skinny_fp8_waves": [_I], "pto_skinny_fp8_tiles": [_I, _I, _I]}
+             "pto_skinny_fp8_waves": [_I], "pto_skinny_fp8_tiles": [_I, _I, _I],
+             "pto_skinny_fused_chains": []}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}
 

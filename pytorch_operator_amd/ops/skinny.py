@@ -10,6 +10,9 @@ Inference only.  On a GPU the HIP kernel runs, and a shape or dtype outside its 
 
 ``quantize_rows`` / ``linear_rows_fp8(x, q, scale, swiglu=False, tiles=0)``: the same on e4m3 weights with a
 power-of-two scale per output row (``csrc/kernels/skinny_gemm_fp8.hip``), under the same rules; see below.
+
+``linear_rows_add_norm`` / ``linear_rows_scaled`` and their ``_fp8`` forms: the decode step's residual add and
+RMSNorm folded into the projections around them (``csrc/kernels/skinny_gemm_fused.hip``); see the end of the file.
 """
 from __future__ import annotations
 
@@ -163,4 +166,168 @@ def launch_rows_fp8(x, q, scale, swiglu: bool = False, tiles: int = 0) -> torch.
     _native.check(_native.load().pto_skinny_fp8_gemm(x2.data_ptr(), q.data_ptr(), scale.data_ptr(), y.data_ptr(),
                                                      x2.shape[0], N, K, int(swiglu), tiles, _stream(x)),
                   "skinny_fp8_gemm")
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The residual add and RMSNorm of a decode step folded into the projections around them
+# (``csrc/kernels/skinny_gemm_fused.hip``).  RMSNorm's row scale commutes with the projection after it, so
+# the GEMM that produces a branch output adds the residual and leaves the next GEMM's operand and the
+# partial sums of squares, and the GEMM that consumes them scales its accumulators by rstd:
+#
+#   h, a, ss = linear_rows_add_norm(x, w, resid, gamma)     h = resid + linear_rows(x, w)   (resid's dtype)
+#                                                           a = bf16(h * gamma), ss[..., t] = sum of h^2 over
+#                                                           the columns 16 t .. 16 t + 15 (fp32)
+#   y = linear_rows_scaled(a, w, ss, eps, swiglu)           rsqrt(ss.sum(-1) / K + eps) * linear_rows(a, w)
+#
+# which is ``linear_rows(rms_norm(h, gamma, eps), w)`` up to the roundings.  The ``_fp8`` forms take
+# ``(q, scale)`` and ``tiles`` as ``linear_rows_fp8`` does.  Same rules as above: HIP on a GPU, ``ValueError``
+# outside the contract, PyTorch on the CPU.
+
+SS_TILE = 16  # columns per partial sum of squares: one MFMA tile
+
+
+def _no_grad(name, *tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise ValueError(f"{name}: inference only (no backward); call it under torch.no_grad()")
+
+
+def _add_norm_contract(x, N, resid, gamma) -> bool:
+    """What both devices ask of the residual epilogue's own operands."""
+    return (resid.dim() == x.dim() and resid.shape[:-1] == x.shape[:-1] and resid.shape[-1] == N
+            and resid.dtype in (torch.float32, torch.bfloat16) and gamma.shape == (N,)
+            and gamma.dtype == torch.float32 and N % SS_TILE == 0)
+
+
+def _add_norm_hip(resid, gamma) -> bool:
+    return (resid.is_cuda and gamma.is_cuda and resid.is_contiguous() and resid.data_ptr() % 16 == 0
+            and gamma.is_contiguous())
+
+
+def _scaled_contract(a, K, ss) -> bool:
+    return (ss.dtype == torch.float32 and K % SS_TILE == 0 and ss.shape == (*a.shape[:-1], K // SS_TILE)
+            and ss.is_contiguous() and ss.device == a.device)
+
+
+def hip_supported_add_norm(x, w, resid, gamma) -> bool:
+    """``hip_supported(x, w)``, and ``resid`` [..., N] fp32 or bf16 with ``x``'s leading shape, contiguous and
+    16-byte aligned; ``gamma`` fp32 [N], contiguous."""
+    return (hip_supported(x, w) and _add_norm_contract(x, w.shape[0], resid, gamma) and _add_norm_hip(resid, gamma))
+
+
+def hip_supported_add_norm_fp8(x, q, scale, resid, gamma, tiles: int = 0) -> bool:
+    return (hip_supported_fp8(x, q, scale, False, tiles) and _add_norm_contract(x, q.shape[0], resid, gamma)
+            and _add_norm_hip(resid, gamma))
+
+
+def hip_supported_scaled(a, w, ss, swiglu: bool = False) -> bool:
+    """``hip_supported(a, w, swiglu)``, and ``ss`` fp32 [..., K / 16] with ``a``'s leading shape, contiguous."""
+    return hip_supported(a, w, swiglu) and _scaled_contract(a, w.shape[1], ss)
+
+
+def hip_supported_scaled_fp8(a, q, scale, ss, swiglu: bool = False, tiles: int = 0) -> bool:
+    return hip_supported_fp8(a, q, scale, swiglu, tiles) and _scaled_contract(a, q.shape[1], ss)
+
+
+def add_norm_reference(d: torch.Tensor, resid: torch.Tensor, gamma: torch.Tensor):
+    """(h, a, ss) of a branch output ``d``: the residual epilogue after the GEMM, in PyTorch."""
+    hf = resid.float() + d.float()
+    ss = hf.reshape(*hf.shape[:-1], -1, SS_TILE).pow(2).sum(-1)
+    return hf.to(resid.dtype), (hf * gamma.float()).to(d.dtype), ss
+
+
+def scaled_reference(a, w, ss, eps: float, swiglu: bool = False) -> torch.Tensor:
+    rstd = torch.rsqrt(ss.sum(-1, keepdim=True) / a.shape[-1] + eps)
+    y = (rstd * F.linear(a.float(), w.float())).to(a.dtype)
+    return swiglu_packed_reference(y) if swiglu else y
+
+
+def _refuse(name, **got):
+    desc = ", ".join(f"{k} {tuple(v.shape)} {v.dtype}" if isinstance(v, torch.Tensor) else f"{k} {v}"
+                     for k, v in got.items())
+    raise ValueError(f"{name}: outside the contract: the plain GEMM's (1 to {max_rows()} rows, bf16 on a GPU), resid "
+                     f"fp32 / bf16 [..., N] contiguous and 16-byte aligned, gamma fp32 [N], ss fp32 "
+                     f"[..., K / {SS_TILE}] contiguous; got {desc}")
+
+
+def linear_rows_add_norm(x, w, resid, gamma):
+    _no_grad("linear_rows_add_norm", x, w, resid, gamma)
+    if not x.is_cuda:
+        if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1] or not 1 <= _rows(x) <= max_rows() \
+                or not _add_norm_contract(x, w.shape[0], resid, gamma):
+            _refuse("linear_rows_add_norm", x=x, w=w, resid=resid, gamma=gamma)
+        return add_norm_reference(linear_rows_reference(x, w), resid, gamma)
+    if not hip_supported_add_norm(x, w, resid, gamma):
+        _refuse("linear_rows_add_norm", x=x, w=w, resid=resid, gamma=gamma, resid_stride=resid.stride())
+    return launch_add_norm(x, w, None, resid, gamma)
+
+
+def linear_rows_add_norm_fp8(x, q, scale, resid, gamma, tiles: int = 0):
+    _no_grad("linear_rows_add_norm_fp8", x, resid, gamma)
+    if not x.is_cuda:
+        if not (_fp8_contract(x, q, scale, False, tiles) and _add_norm_contract(x, q.shape[0], resid, gamma)):
+            _refuse("linear_rows_add_norm_fp8", x=x, q=q, scale=scale, resid=resid, gamma=gamma, tiles=tiles)
+        return add_norm_reference(linear_rows_fp8_reference(x, q, scale), resid, gamma)
+    if not hip_supported_add_norm_fp8(x, q, scale, resid, gamma, tiles):
+        _refuse("linear_rows_add_norm_fp8", x=x, q=q, scale=scale, resid=resid, gamma=gamma, tiles=tiles,
+                resid_stride=resid.stride())
+    return launch_add_norm(x, q, scale, resid, gamma, tiles)
+
+
+def linear_rows_scaled(a, w, ss, eps: float, swiglu: bool = False) -> torch.Tensor:
+    _no_grad("linear_rows_scaled", a, w, ss)
+    if not a.is_cuda:
+        if w.dim() != 2 or a.dim() < 1 or a.shape[-1] != w.shape[1] or not 1 <= _rows(a) <= max_rows() \
+                or (swiglu and w.shape[0] % 2) or not _scaled_contract(a, w.shape[1], ss):
+            _refuse("linear_rows_scaled", a=a, w=w, ss=ss)
+        return scaled_reference(a, w, ss, eps, swiglu)
+    if not hip_supported_scaled(a, w, ss, swiglu):
+        _refuse("linear_rows_scaled", a=a, w=w, ss=ss, swiglu=swiglu)
+    return launch_scaled(a, w, None, ss, eps, swiglu)
+
+
+def linear_rows_scaled_fp8(a, q, scale, ss, eps: float, swiglu: bool = False, tiles: int = 0) -> torch.Tensor:
+    _no_grad("linear_rows_scaled_fp8", a, ss)
+    if not a.is_cuda:
+        if not (_fp8_contract(a, q, scale, swiglu, tiles) and _scaled_contract(a, q.shape[1], ss)):
+            _refuse("linear_rows_scaled_fp8", a=a, q=q, scale=scale, ss=ss, tiles=tiles)
+        return scaled_reference(a, dequantize_rows(q, scale, a.dtype), ss, eps, swiglu)
+    if not hip_supported_scaled_fp8(a, q, scale, ss, swiglu, tiles):
+        _refuse("linear_rows_scaled_fp8", a=a, q=q, scale=scale, ss=ss, swiglu=swiglu, tiles=tiles)
+    return launch_scaled(a, q, scale, ss, eps, swiglu, tiles)
+
+
+def launch_add_norm(x, w, scale, resid, gamma, tiles: int = 0):
+    """The residual-epilogue launch alone (``scale`` None: bf16 weights), for a caller that has just asked the
+    matching ``hip_supported_add_norm*`` about these very arguments."""
+    N, K = w.shape
+    x2 = _aligned(x.reshape(-1, K))
+    h = torch.empty_like(resid)
+    a = torch.empty(resid.shape, dtype=torch.bfloat16, device=resid.device)
+    ss = torch.empty(*resid.shape[:-1], N // SS_TILE, dtype=torch.float32, device=resid.device)
+    lib, bf = _native.load(), int(resid.dtype == torch.bfloat16)
+    if scale is None:
+        rc = lib.pto_skinny_add_norm(x2.data_ptr(), w.data_ptr(), resid.data_ptr(), gamma.data_ptr(), h.data_ptr(),
+                                     a.data_ptr(), ss.data_ptr(), x2.shape[0], N, K, bf, _stream(x))
+    else:
+        rc = lib.pto_skinny_fp8_add_norm(x2.data_ptr(), w.data_ptr(), scale.data_ptr(), resid.data_ptr(),
+                                         gamma.data_ptr(), h.data_ptr(), a.data_ptr(), ss.data_ptr(), x2.shape[0],
+                                         N, K, bf, tiles, _stream(x))
+    _native.check(rc, "skinny_add_norm")
+    return h, a, ss
+
+
+def launch_scaled(a, w, scale, ss, eps: float, swiglu: bool = False, tiles: int = 0) -> torch.Tensor:
+    """The row-scale launch alone, as ``launch_add_norm``."""
+    N, K = w.shape
+    a2 = _aligned(a.reshape(-1, K))
+    y = a.new_empty(*a.shape[:-1], N // 2 if swiglu else N)
+    lib = _native.load()
+    if scale is None:
+        rc = lib.pto_skinny_scaled(a2.data_ptr(), w.data_ptr(), ss.data_ptr(), float(eps), y.data_ptr(), a2.shape[0],
+                                   N, K, int(swiglu), _stream(a))
+    else:
+        rc = lib.pto_skinny_fp8_scaled(a2.data_ptr(), w.data_ptr(), scale.data_ptr(), ss.data_ptr(), float(eps),
+                                       y.data_ptr(), a2.shape[0], N, K, int(swiglu), tiles, _stream(a))
+    _native.check(rc, "skinny_scaled")
     return y

@@ -57,6 +57,10 @@ With hip-fp8 among --decode-linear, ``ops.skinny.linear_rows_fp8`` on ``quantize
 third side ("fp8": its "gbps" counts its own, one-byte weights), and the copies are sized so that the e4m3 ones
 alone exceed 512 MiB.  --fp8-tiles adds one side per forced accumulator count ("fp8_t1", ...), where "fp8" is the
 library's own choice ("tiles").
+
+--linear --fuse-norm: each call of ``csrc/kernels/skinny_gemm_fused.hip`` ("fused") against the launches it replaces
+("unfused"): see ``fused_linear_bench``.  --e2e --fuse-norm [--decode-linear hip,hip-fp8]: ``Llama.generate`` with
+``TNLinear.rows_fuse_norm`` off and on, alternating, two runs each, every run checked by ``TNLinear.rows_calls``.
 """
 import argparse
 import json
@@ -346,6 +350,100 @@ def linear_bench(a):
     return out
 
 
+def fused_linear_bench(a):
+    """Each call of csrc/kernels/skinny_gemm_fused.hip against the launches it replaces, at the decode step's
+    shapes: wo and w2 with the residual epilogue against ``linear_rows`` + ``add_rms_norm`` (two launches), wqkv,
+    w13 + SwiGLU and the lm-head with the row-scale epilogue against ``linear_rows`` alone (the norm they no longer
+    wait for is on the producer's side of the ledger).  bf16 and e4m3 weights, an fp32 residual stream (what
+    ``generate`` carries under autocast), both sides alternating in one process, two runs each."""
+    from pytorch_operator_amd.ops import skinny as S
+    from pytorch_operator_amd.ops.norm import add_rms_norm
+    out = []
+    for name, proj, N, K, swiglu in linear_shapes():
+        wbytes = N * K * 2
+        copies = max(2, -(-(512 << 20) // (wbytes // 2)))
+        ws = torch.empty(copies, N, K, dtype=torch.bfloat16, device="cuda")
+        for i in range(copies):
+            ws[i] = torch.randn(N, K, device="cuda") * 0.02
+        qs = [S.quantize_rows(ws[i]) for i in range(copies)]
+        gamma = 1 + 0.1 * torch.randn(N, device="cuda")
+        for M in a.rows:
+            x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+            resid, ss = torch.randn(M, N, device="cuda"), 8 + 16 * torch.rand(M, K // 16, device="cuda")
+            for fmt in ("bf16", "e4m3"):
+                wa = (lambda i: (ws[i],)) if fmt == "bf16" else (lambda i: qs[i])
+                sfx = "" if fmt == "bf16" else "_fp8"
+                plain = getattr(S, "linear_rows" + sfx)
+                if proj in ("wo", "w2"):
+                    add = getattr(S, "linear_rows_add_norm" + sfx)
+                    fns = {"fused": lambda i: add(x, *wa(i), resid, gamma),
+                           "unfused": lambda i: add_rms_norm(resid, plain(x, *wa(i)), gamma, 1e-5, torch.bfloat16)}
+                else:
+                    scaled = getattr(S, "linear_rows_scaled" + sfx)
+                    fns = {"fused": lambda i: scaled(x, *wa(i), ss, 1e-5, swiglu),
+                           "unfused": lambda i: plain(x, *wa(i), swiglu)}
+                row = {"model": name, "proj": proj, "epilogue": "residual" if proj in ("wo", "w2") else "row-scale",
+                       "weights": fmt, "M": M, "N": N, "K": K, "swiglu": swiglu, "copies": copies}
+                with torch.no_grad():
+                    for side in ("fused", "unfused") * 2:
+                        dev_us, host_us = timed(fns[side], copies, a.reps)
+                        row.setdefault(side + "_us", []).append(round(dev_us, 2))
+                        row.setdefault(side + "_host_us", []).append(round(host_us, 2))
+                print(json.dumps(row), flush=True)
+                out.append(row)
+        del ws, qs
+        torch.cuda.empty_cache()
+    return out
+
+
+def e2e_fused_bench(a):
+    """tokens/s of ``Llama.generate`` with ``TNLinear.rows_fuse_norm`` off (the path without the fused kernels)
+    and on, alternating, for each of --decode-linear's sides (default hip)."""
+    from pytorch_operator_amd.models.llama import CONFIGS, Llama, TNLinear
+    from pytorch_operator_amd.ops.optim import to_bf16_matmul_weights
+    impls = a.decode_linear or ["hip"]
+    out = []
+    for name in a.model:
+        torch.manual_seed(0)
+        with torch.device("cuda"):
+            model = Llama(CONFIGS[name])
+        to_bf16_matmul_weights(model)
+        for p in model.parameters():
+            if hasattr(p, "_pto_master"):
+                del p._pto_master
+        if "hip-fp8" in impls:
+            model.quantize_decode_weights(snap=True)
+        L, steps = model.cfg.n_layers, a.tokens - 1
+        for B in a.batch:
+            prompts = torch.randint(0, model.cfg.vocab_size, (B, a.prompt), device="cuda")
+            for impl in impls:
+                row = {"model": name, "linear": impl, "B": B, "prompt": a.prompt, "new_tokens": a.tokens}
+                for side in ("warm", "off", "on", "off", "on"):
+                    TNLinear.rows_impl, TNLinear.rows_fuse_norm = impl, side != "off"
+                    TNLinear.rows_calls.clear()
+                    try:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        toks = model.generate(prompts, max_new_tokens=a.tokens)
+                        torch.cuda.synchronize()
+                        dt = time.perf_counter() - t0
+                    finally:
+                        TNLinear.rows_impl, TNLinear.rows_fuse_norm = "lib", False
+                    want = {impl: steps * (4 * L + 1) + 1} if side == "off" else \
+                        {impl: steps + 1, impl + "-scaled": steps * 2 * L, impl + "-add-norm": steps * 2 * L,
+                         "rms-norm": steps}
+                    assert dict(TNLinear.rows_calls) == want, TNLinear.rows_calls  # every step took its side's path
+                    if side != "warm":
+                        row.setdefault(side + "_tokens_per_s", []).append(round(B * a.tokens / dt, 1))
+                        row.setdefault(side + "_ms_per_token", []).append(round(dt / a.tokens * 1e3, 3))
+                assert toks.shape == (B, a.tokens)
+                print(json.dumps(row), flush=True)
+                out.append(row)
+        del model
+        torch.cuda.empty_cache()
+    return out
+
+
 def e2e_linear_bench(a):
     """tokens/s of ``Llama.generate`` with the decode step's projections on each side of --decode-linear."""
     from pytorch_operator_amd.models.llama import CONFIGS, Llama, TNLinear
@@ -453,6 +551,10 @@ def main():
                    help="--e2e: the sides of the projection A/B, e.g. lib,hip or lib,hip,hip-fp8 (default: the "
                         "attention A/B); --linear: the sides in their order (default hip,lib)")
     p.add_argument("--fp8-tiles", type=ints, default=[], help="--linear with hip-fp8: also each forced tile count")
+    p.add_argument("--fuse-norm", action="store_true",
+                   help="--linear: each call of skinny_gemm_fused.hip against the launches it replaces; --e2e: "
+                        "generate with the norms folded into the projections against the same without, for "
+                        "--decode-linear's sides (hip and / or hip-fp8; default hip)")
     p.add_argument("--kv", choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the e4m3 KV cache against the bf16 one (kernel mode and --e2e without --decode-linear); with "
                         "--queries: the e4m3 multi-query kernel")
@@ -471,7 +573,11 @@ def main():
         p.error("--fp8-tiles takes 1, 2 and / or 4")
     if a.queries and (a.linear or min(a.queries) < 1):
         p.error("--queries takes positive counts, in the kernel mode or with --e2e")
-    if a.queries and a.e2e:
+    if a.fuse_norm and (not (a.e2e or a.linear) or a.queries or set(a.decode_linear or []) - {"hip", "hip-fp8"}):
+        p.error("--fuse-norm goes with --linear or --e2e, and --decode-linear hip and / or hip-fp8")
+    if a.fuse_norm:
+        res = {"fused_linear": fused_linear_bench(a)} if a.linear else {"e2e_fused": e2e_fused_bench(a)}
+    elif a.queries and a.e2e:
         res = {"steps": steps_bench(a)}
     elif a.queries:
         res = {"queries_fp8": queries_fp8_bench(a)} if a.kv == "fp8" else {"queries": queries_bench(a)}
