@@ -1797,9 +1797,14 @@ constexpr int G_DZS = 82;             // dz row stride (== 18 mod 32: 2a reads 2
 constexpr int G_DZR = 52;             // rows per sample: 50 co + 2 zero rows (2a's K padding to 52)
 constexpr int G_DZN = G_DZR * G_DZS;  // 4264 floats per sample
 constexpr int G_A1S = 2 * F_A1C;      // 2b im2col source per sample: the (at most) 2 channels touched
+// W2-slice row stride (round 9): the staged window itself, 128 columns m = j + cig -- 2a reads no
+// column past it.  2a fetches a lane's four A values of a k row with one ds_read_b128; the bank
+// model has those reads conflict-free at 128 as at the per-sample kernel's 144
+// (tools/lds_banks_fwd.py --only conv_bwd4 --g-ws N)
+constexpr int G_WS = 128;
 constexpr int G_OFF_DZ = 0;
 constexpr int G_OFF_W = G_OFF_DZ + 4 * G_DZN;
-constexpr int G_OFF_DCOL = G_OFF_W + 52 * F_WS;
+constexpr int G_OFF_DCOL = G_OFF_W + 52 * G_WS;
 constexpr int G_OFF_A1 = G_OFF_DCOL + 128 * F_DC;
 constexpr int G_OFF_A1C = G_OFF_A1 + 4 * F_A1C + 12 * F_A1R;
 constexpr int G_OFF_X = G_OFF_A1C + 4 * G_A1S;
@@ -1814,6 +1819,8 @@ constexpr int G_LDS = G_OFF_PV + 4 * 64;
 constexpr int G_OFF_DZ1 = G_OFF_W;            // aliases of the W2 slice (dead after phase 2a)
 constexpr int G_OFF_RED = G_OFF_W + 5 * F_Z1;
 static_assert(G_LDS * 4 <= 160 * 1024, "conv_bwd4 LDS budget");
+static_assert(5 * F_Z1 + 16 * F_RED1 <= 52 * G_WS, "alias region too small");
+static_assert(G_OFF_W % 4 == 0 && G_WS % 4 == 0 && G_WS >= 128, "2a's float4 W2 reads");
 static_assert(G_OFF_PK % 4 == 0 && G_OFF_DZ1 % 4 == 0 && G_OFF_DZ % 2 == 0 && G_DZN % 2 == 0 && G_DZS % 2 == 0, "LDS alignment");
 
 
@@ -1859,28 +1866,38 @@ __device__ __forceinline__ void bwd4_dw1_item_pooled(int it, const float* dp1_s,
   if (kh == 0) pr[125 + c] = bs;
 }
 
-// 2a for wave w of 8: dcolT tiles jt0 .. jt0 + 3 (jt0 = 4 (w >> 2)) x position tile w & 3.
+// 2a for wave w of 8: position tile w & 3 x the 64 window columns m = j + cig of half h = w >> 2,
+// as four 16-row MFMA tiles.  Tile t's row i is column m = 64 h + 4 sig(i) + t with
+// sig(i) = 4 (i & 3) + (i >> 2), so a lane's four A values of a k row are the four consecutive
+// floats at 64 h + 4 sig(i): one aligned ds_read_b128 instead of four ds_read_b32 (round 9; which
+// MFMA row holds a column changes no element's products or their order).  The accumulator row
+// 4 g + rr is then column 64 h + 16 rr + 4 g + t, and dcolT is stored by window column m (col2im
+// reads row j + cig); the g step of 4 rows keeps the stores conflict-free as before.
 // Software-pipelined like 2b below: the LDS operand reads of k-chunk c + 1 are issued before
 // the MFMAs of chunk c (sched_barrier groups keep the compiler from sinking each read to its
 // use, which serialises one LDS round trip per MFMA pair).
 __device__ __forceinline__ void bwd4_2a4(const float* dzc_s, const float* w_s, float* dcol_s, int r, int w,
                                          int lane) {
   const int i = lane & 15, g = lane >> 4;
-  const int pt = w & 3, jt0 = (w >> 2) * 4;
+  const int pt = w & 3, h = w >> 2;
   const float* qa_b = dzc_s + r * G_DZN + g * G_DZS + pt * 16 + i;
-  const float* qa_a = w_s + g * F_WS + jt0 * 16 + i;
-  float ya[13], xa[4][13];
+  const float4* qa_a = reinterpret_cast<const float4*>(w_s + g * G_WS + h * 64) + 4 * (i & 3) + (i >> 2);
+  float ya[13];
+  float4 xa[13];
   f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
 #define A4_R(c)                                                 \
   _Pragma("unroll") for (int s = 4 * (c); s < 4 * (c) + 4; ++s) \
     if (s < 13) {                                               \
       ya[s] = qa_b[4 * s * G_DZS];                              \
-      _Pragma("unroll") for (int t = 0; t < 4; ++t) xa[t][s] = qa_a[4 * s * F_WS + 16 * t]; \
+      xa[s] = qa_a[s * G_WS];                                   \
     }
 #define A4_M(c)                                                 \
   _Pragma("unroll") for (int s = 4 * (c); s < 4 * (c) + 4; ++s) \
     if (s < 13) {                                               \
-      _Pragma("unroll") for (int t = 0; t < 4; ++t) acc[t] = mfma16x16x4(xa[t][s], ya[s], acc[t]); \
+      acc[0] = mfma16x16x4(xa[s].x, ya[s], acc[0]);             \
+      acc[1] = mfma16x16x4(xa[s].y, ya[s], acc[1]);             \
+      acc[2] = mfma16x16x4(xa[s].z, ya[s], acc[2]);             \
+      acc[3] = mfma16x16x4(xa[s].w, ya[s], acc[3]);             \
     }
 #define A4_SB __builtin_amdgcn_sched_barrier(0);
   A4_R(0) A4_SB A4_R(1) A4_SB A4_M(0) A4_SB A4_R(2) A4_SB A4_M(1) A4_SB A4_R(3) A4_SB A4_M(2) A4_SB A4_M(3)
@@ -1888,40 +1905,43 @@ __device__ __forceinline__ void bwd4_2a4(const float* dzc_s, const float* w_s, f
 #undef A4_M
 #undef A4_SB
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) dcol_s[((jt0 + t) * 16 + g * 4 + rr) * F_DC + pt * 16 + i] = acc[t][rr];
+    for (int t = 0; t < 4; ++t) dcol_s[(h * 64 + 16 * rr + 4 * g + t) * F_DC + pt * 16 + i] = acc[t][rr];
 }
 
-// 2b, one K half (samples 2 kh2, 2 kh2 + 1 of the chunk) of dW_conv2 tile pair tp, in four
-// chunks of 8 k-steps, reads one chunk ahead of the MFMAs
-__device__ __forceinline__ f32x4 bwd4_2b(const float* dzc_s, const float* a1c_s, int tp, int kh2, int lane,
-                                         int jbase, int c0) {
+// 2b, one K half of the three co tiles of j tile jt from one im2col read per k-step: every tile
+// keeps bwd4_2b's chain (even / odd k-step accumulators, then e0 + e1).  Eight chunks of 4 k-steps.
+__device__ __forceinline__ void bwd4_2b3(const float* dzc_s, const float* a1c_s, int jt, int kh2, int lane,
+                                         int jbase, int c0, f32x4* out) {
   const int i = lane & 15, g = lane >> 4;
-  const int ct = tp >> 1, jt = tp & 1;
   const int jc = min(max(jbase + jt * 16 + i, 0), 124);
   const int ci = jc / 25, t = jc - ci * 25;
   const float* qb_a = a1c_s + 2 * kh2 * G_A1S + (ci - c0) * F_A1C + (t / 5) * F_A1R + (t % 5) + g;
-  const float* qb_b = dzc_s + 2 * kh2 * G_DZN + (ct * 16 + i) * G_DZS + g;
-  float xb[32], yb[32];
-  f32x4 e0 = zero4(), e1 = zero4();
-#define B2_R(c)                                                   \
-  _Pragma("unroll") for (int u = 8 * (c); u < 8 * (c) + 8; ++u) { \
+  const float* qb_b = dzc_s + 2 * kh2 * G_DZN + i * G_DZS + g;
+  float xb[32], yb[3][32];
+  f32x4 e0[3] = {zero4(), zero4(), zero4()}, e1[3] = {zero4(), zero4(), zero4()};
+#define B3_R(c)                                                   \
+  _Pragma("unroll") for (int u = 4 * (c); u < 4 * (c) + 4; ++u) { \
     const int s_ = u >> 4, uu = u & 15;                           \
     xb[u] = qb_a[s_ * G_A1S + (uu >> 1) * F_A1R + 4 * (uu & 1)];  \
-    yb[u] = qb_b[s_ * G_DZN + 4 * uu];                            \
+    _Pragma("unroll") for (int ct = 0; ct < 3; ++ct) yb[ct][u] = qb_b[s_ * G_DZN + ct * 16 * G_DZS + 4 * uu]; \
   }
-#define B2_M(c)                                                   \
-  _Pragma("unroll") for (int u = 8 * (c); u < 8 * (c) + 8; ++u) { \
-    if (u & 1) e1 = mfma16x16x4(xb[u], yb[u], e1);                \
-    else e0 = mfma16x16x4(xb[u], yb[u], e0);                      \
+#define B3_M(c)                                                   \
+  _Pragma("unroll") for (int u = 4 * (c); u < 4 * (c) + 4; ++u) { \
+    _Pragma("unroll") for (int ct = 0; ct < 3; ++ct) {            \
+      if (u & 1) e1[ct] = mfma16x16x4(xb[u], yb[ct][u], e1[ct]);  \
+      else e0[ct] = mfma16x16x4(xb[u], yb[ct][u], e0[ct]);        \
+    }                                                             \
   }
-#define B2_SB __builtin_amdgcn_sched_barrier(0);
-  B2_R(0) B2_SB B2_R(1) B2_SB B2_M(0) B2_SB B2_R(2) B2_SB B2_M(1) B2_SB B2_R(3) B2_SB B2_M(2) B2_SB B2_M(3)
-#undef B2_R
-#undef B2_M
-#undef B2_SB
-  return e0 + e1;
+#define B3_SB __builtin_amdgcn_sched_barrier(0);
+  B3_R(0) B3_SB B3_R(1) B3_SB B3_M(0) B3_SB B3_R(2) B3_SB B3_M(1) B3_SB B3_R(3) B3_SB B3_M(2) B3_SB B3_R(4) B3_SB
+  B3_M(3) B3_SB B3_R(5) B3_SB B3_M(4) B3_SB B3_R(6) B3_SB B3_M(5) B3_SB B3_R(7) B3_SB B3_M(6) B3_SB B3_M(7)
+#undef B3_R
+#undef B3_M
+#undef B3_SB
+#pragma unroll
+  for (int ct = 0; ct < 3; ++ct) out[ct] = e0[ct] + e1[ct];
 }
 
 __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
@@ -1960,8 +1980,9 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
   // per sample instead of the 12.8 KB dense dz2); with it the W2 slice, the 2b im2col source, the
   // own a1 / idx1 / xn.  Every load is a 16-byte vector (4-byte for idx2), spread over the
   // waves (<= 6 per wave instead of 20 scalar ones), all issued before the first LDS write.
-  // The W2 slice is staged as the aligned float4 window w2[co][124 cig .. 124 cig + 128) and read
-  // at j + cig (2a's rows j >= 125 are garbage-in, never read by col2im).
+  // The W2 slice is staged as the aligned float4 window w2[co][124 cig .. 124 cig + 128), column
+  // m = j + cig; 2a runs on the window's columns (its rows j < 0 and j >= 125 are garbage-in,
+  // never read by col2im).
   float4 pdv = make_float4(0.f, 0.f, 0.f, 0.f), wq1 = pdv, cvv = pdv, avv = pdv, xvv = pdv;
   uint32_t piv = 0u;
   uint4 ivv = make_uint4(0u, 0u, 0u, 0u);
@@ -2015,13 +2036,11 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
     const int s = tid >> 7, rr = 50 + ((tid >> 6) & 1);
     dzc_s[s * G_DZN + rr * G_DZS + (tid & 63)] = 0.f;
   }
-  reinterpret_cast<float4*>(w_s + (tid >> 5) * F_WS)[tid & 31] = wq0;
+  reinterpret_cast<float4*>(w_s + (tid >> 5) * G_WS)[tid & 31] = wq0;
   if (tid < 640) {
     const int co = (tid + 1024) >> 5;
-    reinterpret_cast<float4*>(w_s + co * F_WS)[tid & 31] = co < 50 ? wq1 : make_float4(0.f, 0.f, 0.f, 0.f);
+    reinterpret_cast<float4*>(w_s + co * G_WS)[tid & 31] = co < 50 ? wq1 : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  if (tid >= 960 && tid < 1012)  // window tail (j + cig reads up to m = 130)
-    reinterpret_cast<float4*>(w_s + (tid - 960) * F_WS)[32] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (e_cv >= 0) {
     const int s = e_cv / 72, rem = e_cv - s * 72, c = rem / 36, p4 = rem - c * 36, y = p4 / 3;
     const bool ok = 4 * q + s < B;
@@ -2060,24 +2079,28 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
   // ---- phases 2-4 in two wave groups (round-4 A/B, profiles/r4_bwd4_split_ab.txt: -0.6 us per
   // step).  Waves w and w + 4 share a SIMD, so each SIMD runs two waves of each group:
   //   group B (waves 8-15): all of 2b -- dW_conv2[co, jbase + jl] over the chunk's 4 samples
-  //     (K = 256 positions); waves 8-11 tile pairs 0-3 over both K halves, waves 12-15 tile
-  //     pairs 4-5 one K half each + co 48 / 49 (a fourth 16-row tile would be 7/8 padding) as
-  //     256 VALU dot products; then its slab rows.
+  //     (K = 256 positions); wave 8 + 2 kh + jt runs K half kh of j tile jt for the three co
+  //     tiles from one im2col operand read per k-step (round 9: a third fewer 2b operand reads;
+  //     every tile keeps its chain, half 0 + half 1 meet through pk_s); waves 12-15 co 48 / 49
+  //     (a fourth 16-row tile would be 7/8 padding) as 256 VALU dot products; then its slab rows.
   //   group A (waves 0-7): 2a -- dcolT[j][pos] = W2 slice^T . dz2[b] (M = 128 j, N = 64 pos,
   //     K = 52), four tiles per wave -- then col2im, dW_conv1 and the own sample's slab row:
   //     its VALU phases overlap group B's MFMAs instead of following them behind a barrier.
   // The groups synchronise through LDS arrival counters; per-tile operation order as the
   // one-barrier form: bit-identical.
   if (wv >= 8) {  // ---- group B: all of 2b, then its slab rows
-    const int w8 = wv - 8;
-    const int tpb = w8 < 4 ? w8 : 4 + ((w8 - 4) >> 1), khb = (w8 - 4) & 1;
-    f32x4 gacc;
+    const int w8 = wv - 8, jtb = w8 & 1, khb = (w8 >> 1) & 1;
+    f32x4 hh[3];
     if (w8 < 4) {
-      const f32x4 h0 = bwd4_2b(dzc_s, a1c_s, tpb, 0, lane, jbase, c0);
-      gacc = h0 + bwd4_2b(dzc_s, a1c_s, tpb, 1, lane, jbase, c0);  // K half 0 + K half 1
+      bwd4_2b3(dzc_s, a1c_s, jtb, khb, lane, jbase, c0, hh);
+      // the K halves meet through pk_s: half 1 hands co tiles 0, 1 over, half 0 co tile 2
+      if (khb) {
+        pk_s[jtb * 64 + lane] = hh[0];
+        pk_s[(2 + jtb) * 64 + lane] = hh[1];
+      } else {
+        pk_s[(4 + jtb) * 64 + lane] = hh[2];
+      }
     } else {
-      gacc = bwd4_2b(dzc_s, a1c_s, tpb, khb, lane, jbase, c0);
-      if (khb) pk_s[tpb * 64 + lane] = gacc;
       const int item = tid - 768;  // co 48 / 49 on the VALU, as the barrier form
       const int sm = item >> 6, cr = (item >> 5) & 1, jl = item & 31;
       const int jc = min(max(jbase + jl, 0), 124);
@@ -2093,23 +2116,28 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
     stamp(dbg, 7, 512);  // diagnostics: 2b done (group B), read by tools/step_timeline.py (round 5:
                          // 4.66 us after the stage, when group A has just finished col2im)
     float* rowq = slab + (size_t)q * stride + o_gw2 + cig * 125;
-    if (w8 < 4 || khb == 0) {
-      if (w8 >= 4) gacc += pk_s[tpb * 64 + lane];
-      const int ctb = tpb >> 1, jtb = tpb & 1;
-      float* rp = rowq + (ctb * 16 + i) * 500;
+    if (w8 < 4) {
       const int j0 = jbase + jtb * 16 + 4 * g;
-      if (j0 >= 0 && j0 + 3 < 125) {
-        *reinterpret_cast<float4*>(rp + j0) = make_float4(gacc[0], gacc[1], gacc[2], gacc[3]);
-      } else {
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-          if (j0 + rr >= 0 && j0 + rr < 125) rp[j0 + rr] = gacc[rr];
+      for (int k = 0; k < 2; ++k) {
+        if (khb && k) break;
+        const int ctb = khb ? 2 : k;
+        // K half 0 + K half 1
+        const f32x4 gacc = khb ? pk_s[(4 + jtb) * 64 + lane] + hh[2] : hh[k] + pk_s[(2 * k + jtb) * 64 + lane];
+        float* rp = rowq + (ctb * 16 + i) * 500;
+        if (j0 >= 0 && j0 + 3 < 125) {
+          *reinterpret_cast<float4*>(rp + j0) = make_float4(gacc[0], gacc[1], gacc[2], gacc[3]);
+        } else {
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr)
+            if (j0 + rr >= 0 && j0 + rr < 125) rp[j0 + rr] = gacc[rr];
+        }
       }
     } else if (w8 == 5) {
       const float v = ((pv_s[lane] + pv_s[64 + lane]) + pv_s[128 + lane]) + pv_s[192 + lane];
       const int j = jbase + (lane & 31);
       if (j >= 0 && j < 125) rowq[(48 + (lane >> 5)) * 500 + j] = v;
-    } else if (cig == 0 && own && lane < 50) {  // wave 15: db_conv2 of the own sample, off group A's
+    } else if (w8 == 7 && cig == 0 && own && lane < 50) {  // wave 15: db_conv2 of the own sample, off group A's
       // critical path (on wave 0 of group A it made the cig == 0 blocks 0.5 us slower, profiles/r5_b2)
       const float* dzo = dzc_s + r * G_DZN + lane * G_DZS;
       float b2sum = 0.f;
@@ -2121,13 +2149,13 @@ __global__ __launch_bounds__(F_NT) void conv_bwd4_kernel(
   }
   // ---- group A (waves 0-7): 2a, col2im, dW_conv1, the own sample's slab row
   if (!own) return;
-  bwd4_2a4(dzc_s, w_s + cig, dcol_s, r, wv, lane);
+  bwd4_2a4(dzc_s, w_s, dcol_s, r, wv, lane);
   wave_group_sync(&s_grp[0], 8u);
   stamp(dbg, 2);
   for (int it = tid; it < 720; it += 512) {  // phase 3 (as below)
     const int c = it / 144, p = it - c * 144;
     const int y = p / 12, x = p - y * 12;
-    const float* base = dcol_s + c * 25 * F_DC + y * 8 + x;
+    const float* base = dcol_s + (c * 25 + cig) * F_DC + y * 8 + x;  // dcolT row j + cig
     bool colok[5];
 #pragma unroll
     for (int kw = 0; kw < 5; ++kw) colok[kw] = (x - kw >= 0) & (x - kw <= 7);

@@ -209,7 +209,7 @@ def conv_bwd4(a) -> float:
     4-sample chunk (idx1-dependent phase-4 reads: random pooling argmax)."""
     import random
     rnd = random.Random(7)
-    DZS, DZR, WS, DC, A1R, A1C, XR, RED1 = a.g_dzs, 52, 144, 68, 13, 160, a.g_xr, 132
+    DZS, DZR, WS, DC, A1R, A1C, XR, RED1 = a.g_dzs, 52, a.g_ws, 68, 13, 160, a.g_xr, 132
     DZN = DZR * DZS
     A1S = 2 * A1C
     OFF_W = 4 * DZN
@@ -285,18 +285,18 @@ def conv_bwd4(a) -> float:
                 lanes = range(64)
                 if wv < 8:
                     # ---- 2a
-                    pt, jt0 = wv & 3, (wv >> 2) * 4
+                    # round 9: one float4 of window columns 64 h + 4 sig(i) per k row, dcolT by window column
+                    pt, h = wv & 3, wv >> 2
+                    sig = lambda i: 4 * (i & 3) + (i >> 2)
                     for sstep in range(13):
                         t.add("2a dz2 operand reads", "r32",
                               [r * DZN + (lane >> 4) * DZS + pt * 16 + (lane & 15) + 4 * sstep * DZS for lane in lanes])
-                        for tt in range(4):
-                            t.add("2a W2 operand reads", "r32",
-                                  [OFF_W + cig + (lane >> 4) * WS + jt0 * 16 + (lane & 15) + 4 * sstep * WS + 16 * tt
-                                   for lane in lanes])
+                        t.add("2a W2 operand reads (b128)", "r128",
+                              [OFF_W + ((lane >> 4) + 4 * sstep) * WS + 64 * h + 4 * sig(lane & 15) for lane in lanes])
                     for tt in range(4):
                         for rr in range(4):
                             t.add("2a dcol stores", "w32",
-                                  [OFF_DCOL + ((jt0 + tt) * 16 + (lane >> 4) * 4 + rr) * DC + pt * 16 + (lane & 15)
+                                  [OFF_DCOL + (64 * h + 16 * rr + 4 * (lane >> 4) + tt) * DC + pt * 16 + (lane & 15)
                                    for lane in lanes])
                     # ---- 3: col2im (items tid, tid + 512)
                     for base_it in (0, 512):
@@ -310,7 +310,7 @@ def conv_bwd4(a) -> float:
                                         continue
                                     c, p = it // 144, it % 144
                                     y, x = p // 12, p % 12
-                                    ad.append(OFF_DCOL + c * 25 * DC + y * 8 + x + kh * (5 * DC - 8) + kw * (DC - 1))
+                                    ad.append(OFF_DCOL + (c * 25 + cig) * DC + y * 8 + x + kh * (5 * DC - 8) + kw * (DC - 1))
                                 if any(v is not None for v in ad):
                                     t.add("3 col2im dcol reads", "r32", ad)
                         ad = []
@@ -349,21 +349,23 @@ def conv_bwd4(a) -> float:
                 else:
                     # ---- 2b
                     w8 = wv - 8
-                    calls = [(w8, 0), (w8, 1)] if w8 < 4 else [(4 + ((w8 - 4) >> 1), (w8 - 4) & 1)]
-                    for tp, kh2 in calls:
-                        ct, jt = tp >> 1, tp & 1
+                    # round 9: wave 8 + 2 kh + jt, three co tiles from one im2col read per k-step
+                    if w8 < 4:
+                        jt, kh2 = w8 & 1, w8 >> 1
                         for u in range(32):
                             s_, uu = u >> 4, u & 15
-                            ad_a, ad_b = [], []
+                            ad_a = []
                             for lane in lanes:
                                 i, g = lane & 15, lane >> 4
                                 jc = min(max(jbase + jt * 16 + i, 0), 124)
                                 ci, tt = jc // 25, jc % 25
                                 ad_a.append(OFF_A1C + 2 * kh2 * A1S + (ci - c0) * A1C + (tt // 5) * A1R + tt % 5 + g +
                                             s_ * A1S + (uu >> 1) * A1R + 4 * (uu & 1))
-                                ad_b.append(2 * kh2 * DZN + (ct * 16 + i) * DZS + g + s_ * DZN + 4 * uu)
                             t.add("2b a1 im2col operand reads", "r32", ad_a)
-                            t.add("2b dz2 operand reads", "r32", ad_b)
+                            for ct in range(3):
+                                t.add("2b dz2 operand reads", "r32",
+                                      [2 * kh2 * DZN + (ct * 16 + (lane & 15)) * DZS + (lane >> 4) + s_ * DZN + 4 * uu
+                                       for lane in lanes])
                     if w8 >= 4:
                         items = [64 * wv + ln - 768 for ln in lanes]
                         for pos in range(64):
@@ -391,6 +393,7 @@ def main():
     ap.add_argument("--c2-rs", type=int, default=16)
     ap.add_argument("--c2-ws", type=int, default=514)
     ap.add_argument("--g-dzs", type=int, default=82)
+    ap.add_argument("--g-ws", type=int, default=128, help="conv_bwd4's W2-slice row stride (round 9: 128; 144 before)")
     ap.add_argument("--g-xr", type=int, default=29, help="conv_bwd4's xn row stride (round 6: 30)")
     ap.add_argument("--g-swz", type=int, default=0, help="1: conv_bwd4's un-pool float2 stores row-swapped for ph 2, 3")
     ap.add_argument("--only", default="", help="fc1_bwd_head / conv12_fwd / conv_bwd4: one kernel")
