@@ -29,13 +29,14 @@ def parse_args(argv=None):
                    help="as the worker's: bf16 autocast around the model (a GPU always runs bf16 projections)")
     p.add_argument("--attn", choices=["auto", "sdpa"], default="auto",
                    help="HIP prefill and decode attention where they apply, or the library's")
-    p.add_argument("--decode-linear", choices=["lib", "hip", "hip-fp8"], default="lib",
+    p.add_argument("--decode-linear", choices=["lib", "hip", "hip-fp8", "hip-fp4"], default="lib",
                    help="the decode step's projections and lm-head: the library GEMM, or the skinny HIP GEMM "
                         "(csrc/kernels/skinny_gemm.hip; the nn.Linear weights are cast to bf16 once after loading), "
                         "or hip-fp8: the skinny HIP GEMM on e4m3 weights with a power-of-two scale per output row "
                         "(csrc/kernels/skinny_gemm_fp8.hip; the weights are cast to bf16, quantised once and "
                         "overwritten with their dequantised values, so the model that runs is the quantised one "
-                        "on both the prefill and the decode step)")
+                        "on both the prefill and the decode step), or hip-fp4: the same on OCP MXFP4 weights, e2m1 "
+                        "codes with an e8m0 scale per 32 along K (csrc/kernels/skinny_gemm_fp4.hip)")
     p.add_argument("--decode-fuse-norm", action="store_true",
                    help="with --decode-linear hip or hip-fp8 on a GPU: fold the decode step's residual adds and "
                         "RMSNorms into the projections around them (csrc/kernels/skinny_gemm_fused.hip): 7 launches "
@@ -45,7 +46,10 @@ def parse_args(argv=None):
                         "by csrc/kernels/decode_attention_fp8.hip: half the cache bytes. It quantises k and v, so "
                         "the logits, and with them the tokens, differ from the bf16 cache's")
     p.add_argument("--no-cuda", action="store_true")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.decode_fuse_norm and a.decode_linear == "hip-fp4":
+        p.error("--decode-fuse-norm goes with --decode-linear hip or hip-fp8: there are no fused forms on MXFP4 weights")
+    return a
 
 
 def main(argv=None) -> int:
@@ -68,8 +72,8 @@ def main(argv=None) -> int:
             for mod in model.modules():
                 if isinstance(mod, torch.nn.Linear):
                     mod.weight.data = mod.weight.data.to(torch.bfloat16)
-            if args.decode_linear == "hip-fp8":
-                model.quantize_decode_weights(snap=True)
+            if args.decode_linear in ("hip-fp8", "hip-fp4"):
+                model.quantize_decode_weights(snap=True, fmt=args.decode_linear[-3:])
         gen = torch.Generator(device=dev).manual_seed(args.seed) if args.temperature > 0 else None
         with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=args.dtype == "bf16"):
             toks = model.generate(torch.tensor([prompt], dtype=torch.long, device=dev), max_new_tokens=args.tokens,

@@ -123,10 +123,11 @@ class TNLinear(nn.Linear):
     fp8_grad_format = "e5m2"  # impl "fp8": the output gradient's format (x and w are e4m3)
     # calls with at most ops.skinny.MAX_ROWS rows (a decode step's): "hip" sends them to the skinny
     # GEMM (ops.skinny.linear_rows) where rows_linear() allows, "hip-fp8" to the one on e4m3 weights
-    # (ops.skinny.linear_rows_fp8) for the modules Llama.quantize_decode_weights() has prepared, "lib"
+    # (ops.skinny.linear_rows_fp8) for the modules Llama.quantize_decode_weights() has prepared, "hip-fp4" to
+    # the one on MXFP4 weights (ops.skinny.linear_rows_fp4) after quantize_decode_weights(fmt="fp4"), "lib"
     # leaves every call where it was
     rows_impl = "lib"
-    rows_calls = collections.Counter()  # such calls per path ("hip", "hip-fp8", "lib") on a GPU
+    rows_calls = collections.Counter()  # such calls per path ("hip", "hip-fp8", "hip-fp4", "lib") on a GPU
     # True, with rows_impl "hip" or "hip-fp8": a decode step on a GPU folds its residual adds and RMSNorms
     # into the projections around them (Llama._decode_fused; ops.skinny.linear_rows_add_norm /
     # linear_rows_scaled), counted in rows_calls under rows_impl + "-add-norm" and + "-scaled", and the one
@@ -158,18 +159,26 @@ def rows_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, count_li
     than the GEMM: that case stays where it was) and the shape is inside ``ops.skinny.hip_supported``.
     With ``rows_impl == "hip-fp8"`` it goes to ``ops.skinny.linear_rows_fp8`` under the same conditions on
     ``x``, when ``mod`` (the module that owns ``w``) carries the ``rows_q`` and ``rows_scale`` of
-    ``Llama.quantize_decode_weights`` and the shape is inside ``ops.skinny.hip_supported_fp8``.
+    ``Llama.quantize_decode_weights`` and the shape is inside ``ops.skinny.hip_supported_fp8``; with
+    ``"hip-fp4"`` to ``ops.skinny.linear_rows_fp4`` in the same way, on ``rows_q4`` and ``rows_scale4``.
     Otherwise None: the caller runs the path it always ran.  ``count_lib=False``: that path counts itself."""
     from ..ops import skinny
     if x.numel() > skinny.max_rows() * x.shape[-1]:
         return None
     impl = TNLinear.rows_impl
-    hip = (impl in ("hip", "hip-fp8") and not torch.is_grad_enabled() and
+    hip = (impl in ("hip", "hip-fp8", "hip-fp4") and not torch.is_grad_enabled() and
            (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled("cuda") and
                                           torch.get_autocast_dtype("cuda") == torch.bfloat16)))
     if hip and impl == "hip":
         x = x.to(torch.bfloat16)
         hip = w.dtype == torch.bfloat16 and skinny.hip_supported(x, w, swiglu)
+    elif hip and impl == "hip-fp4":
+        hip = getattr(mod, "rows_q4", None) is not None
+        if hip:
+            if mod.rows_q4.device != x.device:  # plain attributes do not follow Module.to(): once, here
+                mod.rows_q4, mod.rows_scale4 = mod.rows_q4.to(x.device), mod.rows_scale4.to(x.device)
+            x = x.to(torch.bfloat16)
+            hip = skinny.hip_supported_fp4(x, mod.rows_q4, mod.rows_scale4, swiglu)
     elif hip:
         hip = getattr(mod, "rows_q", None) is not None
         if hip:
@@ -183,6 +192,8 @@ def rows_linear(x: torch.Tensor, w: torch.Tensor, swiglu: bool = False, count_li
     TNLinear.rows_calls[impl] += 1
     if impl == "hip":
         return skinny.linear_rows(x, w, swiglu)
+    if impl == "hip-fp4":
+        return skinny.launch_rows_fp4(x, mod.rows_q4, mod.rows_scale4, swiglu)
     return skinny.launch_rows_fp8(x, mod.rows_q, mod.rows_scale, swiglu)
 
 
@@ -291,7 +302,7 @@ class FeedForward(nn.Module):
     def forward(self, x):
         from ..ops.llm import swiglu_packed
         # a decode step: the projection and SwiGLU in one launch
-        if x.is_cuda and TNLinear.rows_impl in ("hip", "hip-fp8"):
+        if x.is_cuda and TNLinear.rows_impl in ("hip", "hip-fp8", "hip-fp4"):
             y = rows_linear(x, self.w13.weight, swiglu=True, count_lib=False, mod=self.w13)
             if y is not None:
                 return self.w2(y)
@@ -363,16 +374,27 @@ class Llama(nn.Module):
         return self.output(y) if out is None else out
 
     @torch.no_grad()
-    def quantize_decode_weights(self, snap: bool = True) -> int:
+    def quantize_decode_weights(self, snap: bool = True, fmt: str = "fp8") -> int:
         """Prepare ``TNLinear.rows_impl = "hip-fp8"``: every ``TNLinear`` and ``output`` gets ``rows_q`` (e4m3
         [N, K]) and ``rows_scale`` (fp32 [N], powers of two) of ``ops.skinny.quantize_rows`` as plain
         attributes -- neither parameters nor buffers, so state-dict keys and checkpoints do not change.
         ``snap``: the weight itself is overwritten in place with the dequantised value (exact in bf16), so
         the prefill (library GEMM on the weight) and the decode step (the kernel on ``rows_q``) run the same
-        model.  The weights are kept: memory goes up by a byte per weight.  Returns the number of modules."""
-        from ..ops.skinny import dequantize_rows, quantize_rows
+        model.  The weights are kept: memory goes up by a byte per weight.  Returns the number of modules.
+        ``fmt="fp4"`` prepares ``rows_impl = "hip-fp4"`` instead: ``rows_q4`` (uint8 [N, K / 2]) and
+        ``rows_scale4`` (e8m0 [N, K / 32]) of ``ops.skinny.quantize_rows_fp4``, beside the e4m3 attributes if
+        they are there, and ``snap`` overwrites the weight with their dequantised value; memory goes up by 17 / 32
+        of a byte per weight."""
+        from ..ops.skinny import dequantize_rows, dequantize_rows_fp4, quantize_rows, quantize_rows_fp4
+        if fmt not in ("fp8", "fp4"):
+            raise ValueError(f"quantize_decode_weights: fmt is 'fp8' or 'fp4'; got {fmt!r}")
         mods = [m for m in self.modules() if isinstance(m, TNLinear)] + [self.output]
         for m in mods:
+            if fmt == "fp4":
+                m.rows_q4, m.rows_scale4 = quantize_rows_fp4(m.weight)
+                if snap:
+                    m.weight.copy_(dequantize_rows_fp4(m.rows_q4, m.rows_scale4, m.weight.dtype))
+                continue
             m.rows_q, m.rows_scale = quantize_rows(m.weight)
             if snap:
                 m.weight.copy_(dequantize_rows(m.rows_q, m.rows_scale, m.weight.dtype))

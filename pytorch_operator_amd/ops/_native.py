@@ -217,6 +217,8 @@ _SIGNATURES = {
     "pto_skinny_gemm": [_VP, _VP, _VP, _I, _I, _I, _I, _VP],
     # skinny_gemm_fp8.hip
     "pto_skinny_fp8_gemm": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP],
+    # skinny_gemm_fp4.hip
+    "pto_skinny_fp4_gemm": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP],
     # skinny_gemm_fused.hip
     "pto_skinny_add_norm": [_VP] * 7 + [_I, _I, _I, _I, _VP],
     "pto_skinny_fp8_add_norm": [_VP] * 8 + [_I, _I, _I, _I, _I, _VP],
@@ -270,6 +272,7 @@ _LONG_FNS = {"pto_xar_npad": [_VP], "pto_xar_emu_npad": [_VP], "pto_rmsnorm_bwd_
              "pto_grad_accum_sweep": [], "pto_token_batch_chunk": [], "pto_decode_chunk": [], "pto_decode_multi_rows": [],
              "pto_skinny_max_rows": [], "pto_skinny_waves": [_I],
              "pto_skinny_fp8_waves": [_I], "pto_skinny_fp8_tiles": [_I, _I, _I],
+             "pto_skinny_fp4_waves": [_I], "pto_skinny_fp4_tiles": [_I, _I, _I],
              "pto_skinny_fused_chains": []}
 _VOID_FNS = {"pto_set_debug_buffer": [_VP], "pto_xar_emu_stamps": [_VP, _VP]}
 _PTR_FNS = {"pto_xar_err_ptr": [_VP]}

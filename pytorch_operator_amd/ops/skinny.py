@@ -11,6 +11,9 @@ Inference only.  On a GPU the HIP kernel runs, and a shape or dtype outside its 
 ``quantize_rows`` / ``linear_rows_fp8(x, q, scale, swiglu=False, tiles=0)``: the same on e4m3 weights with a
 power-of-two scale per output row (``csrc/kernels/skinny_gemm_fp8.hip``), under the same rules; see below.
 
+``quantize_rows_fp4`` / ``linear_rows_fp4(x, q, scale, swiglu=False, tiles=0)``: the same on OCP MXFP4 weights, e2m1
+codes with an e8m0 scale per 32 along K (``csrc/kernels/skinny_gemm_fp4.hip``), under the same rules; see below.
+
 ``linear_rows_add_norm`` / ``linear_rows_scaled`` and their ``_fp8`` forms: the decode step's residual add and
 RMSNorm folded into the projections around them (``csrc/kernels/skinny_gemm_fused.hip``); see the end of the file.
 """
@@ -166,6 +169,116 @@ def launch_rows_fp8(x, q, scale, swiglu: bool = False, tiles: int = 0) -> torch.
     _native.check(_native.load().pto_skinny_fp8_gemm(x2.data_ptr(), q.data_ptr(), scale.data_ptr(), y.data_ptr(),
                                                      x2.shape[0], N, K, int(swiglu), tiles, _stream(x)),
                   "skinny_fp8_gemm")
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------------
+# MXFP4 weights (``csrc/kernels/skinny_gemm_fp4.hip``): OCP e2m1 codes, two to a byte, in blocks of 32 along K with
+# one e8m0 power-of-two scale per block, bf16 activations, fp32 accumulation -- 17 / 32 of a byte per weight.  An
+# e2m1 value times a power of two is exact in bf16: ``dequantize_rows_fp4(q, scale)`` is a bf16 matrix, and
+# ``linear_rows_fp4(x, q, scale)`` is ``linear_rows`` on it.
+
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitudes of a code's bits 0-2; bit 3 is the sign
+FP4_BLOCK = 32
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """2^e in fp32 for integer ``e`` in [-126, 127], from the bits."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def quantize_rows_fp4(w: torch.Tensor):
+    """``w`` [N, K], K % 32 == 0 -> (``q`` uint8 [N, K / 2], ``scale`` uint8 [N, K / 32]), both contiguous.  Byte j
+    of a row of ``q`` holds the code of k = 2 j in its low nibble and of k = 2 j + 1 in its high one.  ``scale`` is
+    e8m0: byte b means 2^(b - 127), with b - 127 = e = ceil(log2(amax / 6)) of the block clamped to [-125, 125]
+    (0 for a zero block), so that the quotient is inside +-6 and every non-zero dequantised value is a normal bf16.
+    A code is ``w / 2^e`` rounded to the nearest magnitude, ties to the even index, sign kept; 0x8 is never emitted."""
+    if w.dim() != 2 or w.shape[1] % FP4_BLOCK or not w.is_floating_point():
+        raise ValueError(f"quantize_rows_fp4: w [N, K] with K % {FP4_BLOCK} == 0; got {tuple(w.shape)} {w.dtype}")
+    N, K = w.shape
+    wf = w.detach()
+    wf = (wf if wf.dtype == torch.float64 else wf.float()).reshape(N, K // FP4_BLOCK, FP4_BLOCK)
+    amax = wf.abs().amax(dim=-1)
+    m, ex = torch.frexp(amax)                          # amax = m 2^ex, m in [0.5, 1)
+    e = torch.where(m <= 0.75, ex - 3, ex - 2)         # the least e with amax <= 6 * 2^e = 0.75 * 2^(e + 3)
+    e = torch.where(amax > 0, e.clamp(-125, 125), torch.zeros_like(e))
+    a = (wf * _pow2(-e).to(wf.dtype)[..., None]).abs()  # exact: at worst a value under 2^-126 in fp32, a zero code
+    idx = torch.zeros_like(a, dtype=torch.uint8)
+    for i in range(7):                                  # past the midpoint to the next magnitude; a tie goes to even
+        mid = (E2M1[i] + E2M1[i + 1]) / 2
+        idx += (a >= mid) if i % 2 else (a > mid)
+    code = (idx | (((wf < 0) & (idx > 0)).to(torch.uint8) << 3)).reshape(N, K)
+    q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return q, (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_rows_fp4(q: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """The [N, K] matrix that ``(q, scale)`` means, in ``dtype``: exact in bf16 and anything wider.  Code 0x8 reads
+    as zero.  A table lookup and a multiply by a power of two built from its bits."""
+    if q.dim() != 2 or q.dtype != torch.uint8 or scale.dtype != torch.uint8 \
+            or scale.shape != (q.shape[0], q.shape[1] * 2 // FP4_BLOCK) or q.shape[1] * 2 % FP4_BLOCK:
+        raise ValueError(f"dequantize_rows_fp4: q uint8 [N, K / 2] and scale uint8 [N, K / {FP4_BLOCK}]; got "
+                         f"{tuple(q.shape)} {q.dtype}, {tuple(scale.shape)} {scale.dtype}")
+    N, K = q.shape[0], q.shape[1] * 2
+    lut = torch.tensor(E2M1 + (0.0,) + tuple(-v for v in E2M1[1:]), dtype=torch.float32, device=q.device)
+    v = lut[torch.stack((q & 15, q >> 4), dim=-1).reshape(N, K // FP4_BLOCK, FP4_BLOCK).long()]
+    return (v * _pow2(scale.to(torch.int32) - 127)[..., None]).reshape(N, K).to(dtype)
+
+
+def _fp4_contract(x, q, scale, swiglu, tiles) -> bool:
+    """What both devices ask: shapes, dtypes of q and scale, tiles."""
+    if q.dim() != 2 or x.dim() < 1 or x.shape[-1] != 2 * q.shape[1] or q.dtype != torch.uint8 \
+            or scale.dtype != torch.uint8 or tiles not in FP8_TILES:
+        return False
+    N, K = q.shape[0], 2 * q.shape[1]
+    return (1 <= _rows(x) <= max_rows() and N > 0 and N % (32 if swiglu else 16) == 0 and K % 128 == 0
+            and scale.shape == (N, K // FP4_BLOCK) and q.is_contiguous() and scale.is_contiguous())
+
+
+def hip_supported_fp4(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+                      tiles: int = 0) -> bool:
+    """The kernel's contract: bf16 CUDA ``x``, 1..MAX_ROWS rows; ``q`` uint8 [N, K / 2], contiguous and 16-byte
+    aligned; ``scale`` uint8 [N, K / 32], contiguous and 2-byte aligned (the kernel loads a step's two scale bytes at
+    once; the rows are multiples of 4 bytes); N % 16 == 0 (N % 32 == 0 with ``swiglu``), K % 128 == 0; ``tiles`` in
+    ``FP8_TILES``; no gradient asked for."""
+    if not (x.is_cuda and q.is_cuda and scale.is_cuda) or x.dtype != torch.bfloat16:
+        return False
+    if torch.is_grad_enabled() and x.requires_grad:
+        return False
+    return _fp4_contract(x, q, scale, swiglu, tiles) and q.data_ptr() % 16 == 0 and scale.data_ptr() % 2 == 0
+
+
+def linear_rows_fp4_reference(x, q, scale, swiglu: bool = False) -> torch.Tensor:
+    y = F.linear(x, dequantize_rows_fp4(q, scale, x.dtype))
+    return swiglu_packed_reference(y) if swiglu else y
+
+
+def linear_rows_fp4(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, swiglu: bool = False,
+                    tiles: int = 0) -> torch.Tensor:
+    """``linear_rows(x, dequantize_rows_fp4(q, scale), swiglu)`` from the packed bytes.  ``tiles`` forces the
+    accumulators per wave (tests, benchmarks); the result does not depend on it."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise ValueError("linear_rows_fp4: inference only (no backward); call it under torch.no_grad()")
+    ok = hip_supported_fp4(x, q, scale, swiglu, tiles) if x.is_cuda else _fp4_contract(x, q, scale, swiglu, tiles)
+    if not ok:
+        raise ValueError(f"linear_rows_fp4: x [..., K] of 1 to {max_rows()} rows (bf16 on a GPU), q [N, K / 2] uint8, "
+                         f"contiguous and 16-byte aligned, scale [N, K / {FP4_BLOCK}] uint8, contiguous and 2-byte "
+                         f"aligned, N % {32 if swiglu else 16} == 0, K % 128 == 0, tiles in {FP8_TILES}; got x "
+                         f"{tuple(x.shape)} {x.dtype}, q {tuple(q.shape)} {q.dtype} stride {q.stride()}, scale "
+                         f"{tuple(scale.shape)} {scale.dtype}, tiles {tiles}")
+    if not x.is_cuda:
+        return linear_rows_fp4_reference(x, q, scale, swiglu)
+    return launch_rows_fp4(x, q, scale, swiglu, tiles)
+
+
+def launch_rows_fp4(x, q, scale, swiglu: bool = False, tiles: int = 0) -> torch.Tensor:
+    """The launch alone, for a caller that has just asked ``hip_supported_fp4`` about these very arguments."""
+    N, K = q.shape[0], 2 * q.shape[1]
+    x2 = _aligned(x.reshape(-1, K))
+    y = x.new_empty(*x.shape[:-1], N // 2 if swiglu else N)
+    _native.check(_native.load().pto_skinny_fp4_gemm(x2.data_ptr(), q.data_ptr(), scale.data_ptr(), y.data_ptr(),
+                                                     x2.shape[0], N, K, int(swiglu), tiles, _stream(x)),
+                  "skinny_fp4_gemm")
     return y
 
 

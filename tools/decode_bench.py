@@ -8,7 +8,7 @@ usage: python tools/decode_bench.py [--batch 1,8] [--keys 512,2048,8192] [--head
        python tools/decode_bench.py --queries 2,4 [--batch 1,8] [--keys 512,2048,8192] [--head-dim 64,128]
        python tools/decode_bench.py --e2e --queries 2,4 [--model llama3-1b,llama3-8b] [--batch 1,2,4,8] [--prompt 128]
        python tools/decode_bench.py --queries 1,2,4 --kv fp8 [--e2e] [...]
-       python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200] [--decode-linear hip-fp8,hip,lib]
+       python tools/decode_bench.py --linear [--rows 1,8,16] [--reps 200] [--decode-linear hip-fp4,hip-fp8,hip,lib]
                                              [--fp8-tiles 1,2,4]
 
 Kernel mode: one ``decode_attention`` call per cache layer, ``--reps`` calls back to back between two
@@ -55,7 +55,8 @@ of the weight to exceed 512 MiB, so every call streams its weight from HBM ("gbp
 = that over 8 TB/s); sides alternate, two runs each, with the host's issue time beside the device's as above.
 With hip-fp8 among --decode-linear, ``ops.skinny.linear_rows_fp8`` on ``quantize_rows`` of the same weights is a
 third side ("fp8": its "gbps" counts its own, one-byte weights), and the copies are sized so that the e4m3 ones
-alone exceed 512 MiB.  --fp8-tiles adds one side per forced accumulator count ("fp8_t1", ...), where "fp8" is the
+alone exceed 512 MiB.  hip-fp4 adds ``ops.skinny.linear_rows_fp4`` on ``quantize_rows_fp4`` of the same weights in
+the same way ("fp4": its "gbps" counts its codes and scale bytes, 17 / 32 of a byte a weight).  --fp8-tiles adds one side per forced accumulator count ("fp8_t1", ...), where "fp8" is the
 library's own choice ("tiles").
 
 --linear --fuse-norm: each call of ``csrc/kernels/skinny_gemm_fused.hip`` ("fused") against the launches it replaces
@@ -308,25 +309,30 @@ def linear_shapes():
 def linear_bench(a):
     from pytorch_operator_amd.ops import _native
     from pytorch_operator_amd.ops.llm import swiglu_packed
-    from pytorch_operator_amd.ops.skinny import linear_rows, linear_rows_fp8, quantize_rows
-    fp8 = "hip-fp8" in (a.decode_linear or [])
-    sides = [{"hip-fp8": "fp8"}.get(s, s) for s in (a.decode_linear or ["hip", "lib"])]
+    from pytorch_operator_amd.ops.skinny import (linear_rows, linear_rows_fp4, linear_rows_fp8, quantize_rows,
+                                                 quantize_rows_fp4)
+    fp8, fp4 = "hip-fp8" in (a.decode_linear or []), "hip-fp4" in (a.decode_linear or [])
+    sides = [{"hip-fp8": "fp8", "hip-fp4": "fp4"}.get(s, s) for s in (a.decode_linear or ["hip", "lib"])]
     sides = sides[:1] + [f"fp8_t{t}" for t in a.fp8_tiles if fp8] + sides[1:]
     lib = _native.load()
     out = []
     for name, proj, N, K, swiglu in linear_shapes():
         wbytes = N * K * 2
-        copies = max(2, -(-(512 << 20) // (wbytes // 2 if fp8 else wbytes)))
+        own = {"fp4": wbytes * 17 // 64, "fp8": wbytes // 2}   # fp4: half a byte a weight and a scale byte per 32
+        copies = max(2, -(-(512 << 20) // (own["fp4"] if fp4 else own["fp8"] if fp8 else wbytes)))
         ws = torch.empty(copies, N, K, dtype=torch.bfloat16, device="cuda")
         for i in range(copies):  # a copy at a time: the fp32 draw of all of them would be 4 bytes a weight
             ws[i] = torch.randn(N, K, device="cuda") * 0.02
         if fp8:
             qs = [quantize_rows(ws[i]) for i in range(copies)]
+        if fp4:
+            q4 = [quantize_rows_fp4(ws[i]) for i in range(copies)]
         for M in a.rows:
             x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
             fns = {"hip": lambda i: linear_rows(x, ws[i], swiglu),
                    "lib": (lambda i: swiglu_packed(F.linear(x, ws[i]))) if swiglu else (lambda i: F.linear(x, ws[i])),
-                   "fp8": lambda i: linear_rows_fp8(x, *qs[i], swiglu)}
+                   "fp8": lambda i: linear_rows_fp8(x, *qs[i], swiglu),
+                   "fp4": lambda i: linear_rows_fp4(x, *q4[i], swiglu)}
             for t in a.fp8_tiles:
                 fns[f"fp8_t{t}"] = lambda i, t=t: linear_rows_fp8(x, *qs[i], swiglu, t)
             row = {"model": name, "proj": proj, "M": M, "N": N, "K": K, "swiglu": swiglu, "copies": copies,
@@ -334,14 +340,16 @@ def linear_bench(a):
             if fp8:
                 row.update(fp8_footprint_mb=round(copies * wbytes / 2e6, 1),
                            tiles=int(lib.pto_skinny_fp8_tiles(M, N, int(swiglu))))
+            if fp4:
+                row.update(fp4_footprint_mb=round(copies * own["fp4"] / 1e6, 1))
             with torch.no_grad():
                 for side in sides * 2:
                     dev_us, host_us = timed(fns[side], copies, a.reps)
                     row.setdefault(side + "_us", []).append(round(dev_us, 2))
                     row.setdefault(side + "_host_us", []).append(round(host_us, 2))
             for side in sides:
-                own = wbytes // 2 if side.startswith("fp8") else wbytes
-                row[side + "_gbps"] = round(own / min(row[side + "_us"]) / 1e3, 1)
+                mine = own.get(side[:3], wbytes)
+                row[side + "_gbps"] = round(mine / min(row[side + "_us"]) / 1e3, 1)
                 row[side + "_peak"] = round(row[side + "_gbps"] / 8000.0, 3)
             print(json.dumps(row), flush=True)
             out.append(row)
@@ -459,10 +467,16 @@ def e2e_linear_bench(a):
                 del p._pto_master  # the fp32 copy an optimizer would take over: not needed here
         if "hip-fp8" in a.decode_linear:
             model.quantize_decode_weights(snap=True)  # every side then runs the same, quantised, model
+        if "hip-fp4" in a.decode_linear:
+            # alone, the same; beside hip-fp8 the weights stay the e4m3 model's and the fp4 side runs its own
+            # quantisation of them: the time of a step does not depend on the values
+            model.quantize_decode_weights(snap="hip-fp8" not in a.decode_linear, fmt="fp4")
         L = model.cfg.n_layers
         for B in a.batch:
             prompts = torch.randint(0, model.cfg.vocab_size, (B, a.prompt), device="cuda")
             row = {"model": name, "B": B, "prompt": a.prompt, "new_tokens": a.tokens}
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()  # after the quantisation's temporaries
             for i, side in enumerate(["warm"] + a.decode_linear * 2):
                 TNLinear.rows_impl = a.decode_linear[0] if side == "warm" else side
                 TNLinear.rows_calls.clear()
@@ -482,6 +496,7 @@ def e2e_linear_bench(a):
                     row.setdefault(side + "_tokens_per_s", []).append(round(B * a.tokens / dt, 1))
                     row.setdefault(side + "_ms_per_token", []).append(round(dt / a.tokens * 1e3, 3))
             assert toks.shape == (B, a.tokens)
+            row["peak_mem_mb"] = round(torch.cuda.max_memory_allocated() / 1e6, 1)  # the weights of every side, and the caches
             print(json.dumps(row), flush=True)
             out.append(row)
         del model
@@ -565,8 +580,8 @@ def main():
     a = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: needs a GPU (a CPU timing says nothing about these kernels)")
-    if a.decode_linear and (not (a.e2e or a.linear) or set(a.decode_linear) - {"lib", "hip", "hip-fp8"}):
-        p.error("--decode-linear takes lib, hip and / or hip-fp8, with --e2e or --linear")
+    if a.decode_linear and (not (a.e2e or a.linear) or set(a.decode_linear) - {"lib", "hip", "hip-fp8", "hip-fp4"}):
+        p.error("--decode-linear takes lib, hip, hip-fp8 and / or hip-fp4, with --e2e or --linear")
     if a.kv == "fp8" and (a.linear or a.decode_linear):
         p.error("--kv fp8 goes with the kernel mode or the attention --e2e")
     if set(a.fp8_tiles) - {1, 2, 4}:
